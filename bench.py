@@ -1,8 +1,17 @@
 #!/usr/bin/env python3
 """Headline benchmark: V-cycle grid-point-updates/sec at N=16384 (BASELINE.json).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, runs W warm-up steps, times K steps once and prints the
+result line (value, ms_per_step, the dominant kernel's roofline from the HIP
+events of the timed region).  --dump-outputs DIR then writes what the last
+timed step left a caller: DIR/u.npy (the finest-level solution; above 32 MB a
+fixed, seeded sample of its points) and DIR/residual.npy (the step's residual
+norm), float64.  --full adds everything else described below (5 repetitions
+with the median as value, GPU clocks, per-kernel breakdown, host-buffer rate,
+the other fp_mode / velocity-path / tower runs, stream ceilings, CPU baseline).
 
 A step = one V-cycle (mg_inner, multigrid.cpp:17-92) + the residual and norm
 mg_outer computes after it (multigrid.cpp:112-113), with a fixed cycle count
@@ -152,8 +161,14 @@ def parse():
                     help="arithmetic of the smoothing passes (mgx_options.fp_mode): fma = "
                          "contracted, within 1e-12 of the reference; bitwise = the reference's "
                          "bits")
-    ap.add_argument("--reps", type=int, default=5,
-                    help="timed repetitions of --steps cycles; value = the median (SURVEY 8d)")
+    ap.add_argument("--reps", type=int, default=0,
+                    help="timed repetitions of --steps cycles; value = the median (SURVEY 8d); "
+                         "0: 1, or 5 with --full")
+    ap.add_argument("--full", action="store_true",
+                    help="also: 5 repetitions, GPU clocks, per-kernel breakdown, host-buffer "
+                         "rate, comparison runs, stream ceilings, CPU baseline")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write the last step's outputs to DIR/*.npy")
     ap.add_argument("--no-compare", "--no-generic", action="store_true", dest="no_compare",
                     help="skip the comparison runs (other fp_mode, generic velocity path)")
     ap.add_argument("--no-profile", action="store_true",
@@ -168,7 +183,10 @@ def parse():
                     help="N > 1: deadline of each phase that waits on peers (RCCL self-check, "
                          "set-up, overlap pricing, timed region); on expiry the rank prints an "
                          "error JSON line and exits 1 instead of hanging")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.reps <= 0:
+        args.reps = 5 if args.full else 1
+    return args
 
 
 def velocity_note(mask, correct, L):
@@ -473,6 +491,29 @@ def sweep(args):
     print(json.dumps(out), flush=True)
 
 
+DUMP_WHOLE_BYTES = 32 << 20   # a larger solution is dumped as a sample of this size
+DUMP_SEED = 16384
+
+
+def dump_outputs(dirname, u, res, rank=0, world=1):
+    """--dump-outputs: what the last timed step left a caller, float64 .npy
+    files.  u: this rank's rows of the finest-level solution (the whole grid on
+    one GPU), whole up to DUMP_WHOLE_BYTES (over all ranks), above that its
+    values at point indices drawn once from a fixed seed (sorted; the same
+    points for the same N and rank count, whatever the build); res: the
+    step's residual norm."""
+    os.makedirs(dirname, exist_ok=True)
+    tag = f"_rank{rank}" if world > 1 else ""
+    keep = DUMP_WHOLE_BYTES // 8 // world
+    if u.size > keep:
+        idx = np.random.default_rng([DUMP_SEED, rank]).integers(0, u.size, keep)
+        idx.sort()
+        u = u[idx]
+    np.save(os.path.join(dirname, f"u{tag}.npy"), np.ascontiguousarray(u, dtype=np.float64))
+    if rank == 0:
+        np.save(os.path.join(dirname, "residual.npy"), np.array([res], dtype=np.float64))
+
+
 def main():
     args = parse()
     if args.sweep:
@@ -594,7 +635,11 @@ def main():
 
     gpu_state = GpuState(local)
 
-    def timed_reps(m, reps, prof, state=None):
+    # --full's further measurements run at most this many cycles per repetition,
+    # so a long headline run does not multiply through them
+    side_steps = min(args.steps, 500)
+
+    def timed_reps(m, reps, prof, state=None, steps=args.steps):
         """SURVEY 8(d) protocol: `reps` repetitions of K cycles, each bracketed
         by barrier + synchronize, max over ranks; HIP events around the
         finest-level launches (prof); the GPU's clocks sampled after each
@@ -612,7 +657,7 @@ def main():
             # K steps = K V-cycles, each followed by its residual norm (read
             # back per cycle, as mg_outer does); the K-th cycle's solution is
             # materialised
-            res = m.run_cycles(args.steps)
+            res = m.run_cycles(steps)
             m.synchronize()
             barrier()
             torch.cuda.synchronize()
@@ -632,15 +677,20 @@ def main():
         return best
 
     with watch("timed region"):
-        rep_s, res = timed_reps(mg, args.reps, not args.no_profile, gpu_state)
+        rep_s, res = timed_reps(mg, args.reps, not args.no_profile,
+                                gpu_state if args.full else None)
     elapsed = sorted(rep_s)[len(rep_s) // 2]   # the median repetition
     best = dominant(mg)
     mg.profile(False)
+    if args.dump_outputs:
+        # before anything below runs further cycles on this context
+        dump_outputs(args.dump_outputs, mg.download_rows(0) if world > 1 else mg.download(),
+                     res, rank, world)
 
     # per-kernel, per-level breakdown: a few more cycles, every launch timed
     # (after the timed region, so its event overhead is not in `value`)
     kernels = {}
-    if not args.no_profile:
+    if args.full and not args.no_profile:
         prof_steps = 3
         mg.profile_reset()
         mg.profile(True)
@@ -664,7 +714,7 @@ def main():
     if world == 1:
         _lib.check(_lib.lib().mgx_velocity_factored(mg.handle, ctypes.byref(fac)))
     pcie = None
-    if world == 1 and not row_upload:
+    if args.full and world == 1 and not row_upload:
         # the boundary's host-buffer rate (never `value`): the same K cycles
         # with the host arrays handed over before (mgx_upload: H2D copies +
         # the device-built tower + the upload-time velocity checks) and the
@@ -678,7 +728,7 @@ def main():
         t_up = time.perf_counter() - t0
         mg.rhs()
         t1 = time.perf_counter()
-        mg.run_cycles(args.steps)
+        mg.run_cycles(side_steps)
         mg.synchronize()
         t_cyc = time.perf_counter() - t1
         t2 = time.perf_counter()
@@ -687,8 +737,8 @@ def main():
         del u0, v1, v2, uo
         pcie = {"upload_s": round(t_up, 4), "cycles_s": round(t_cyc, 5),
                 "download_s": round(t_down, 4),
-                "value_incl": (N - 1) ** 2 * args.steps / (t_up + t_cyc + t_down),
-                "note": f"{args.steps} V-cycles with mgx_upload (3 host arrays of "
+                "value_incl": (N - 1) ** 2 * side_steps / (t_up + t_cyc + t_down),
+                "note": f"{side_steps} V-cycles with mgx_upload (3 host arrays of "
                         f"{(N + 1) ** 2 * 8 / 1e9:.2f} GB: H2D + tower + velocity checks) "
                         f"before and mgx_download after, inside the clock; the bench value "
                         f"starts with the inputs resident in HBM"}
@@ -770,7 +820,7 @@ def main():
             g.rhs()
             g.run_cycles(2)
             g.synchronize()
-            secs, _ = timed_reps(g, reps, True)
+            secs, _ = timed_reps(g, reps, True, steps=side_steps)
             b = dominant(g)
             g.profile(False)
             g.close()
@@ -780,9 +830,9 @@ def main():
         med = sorted(secs)[len(secs) // 2]
         mode = ("fma" if fpm == _lib.FP_FMA else "bitwise") + \
                ("-generic" if tuning.get("sep_velocity") == 0 else "")
-        return {"label": label, "ms_per_step": round(med / args.steps * 1e3, 4),
-                "rep_ms_per_step": [round(x / args.steps * 1e3, 4) for x in secs],
-                "value": (N - 1) ** 2 * args.steps / med,
+        return {"label": label, "ms_per_step": round(med / side_steps * 1e3, 4),
+                "rep_ms_per_step": [round(x / side_steps * 1e3, 4) for x in secs],
+                "value": (N - 1) ** 2 * side_steps / med,
                 "roofline": roofline(b, mode) if b else None}
 
     fp_name = "fma" if fp == _lib.FP_FMA else "bitwise"
@@ -790,7 +840,7 @@ def main():
     generic = None
     nonrank1 = None
     correct = None
-    if world == 1 and not args.no_compare:
+    if args.full and world == 1 and not args.no_compare:
         # the other arithmetic mode (bitwise: every value the reference's)
         ofp = _lib.FP_BITWISE if fp == _lib.FP_FMA else _lib.FP_FMA
         other = side_run("bitwise" if ofp == _lib.FP_BITWISE else "fma", ofp, {}, 3)
@@ -822,7 +872,7 @@ def main():
     value = (N - 1) ** 2 * args.steps / elapsed
     # SURVEY 8d secondary metric: RB-GS point updates per second
     smoother_pts = sum(2 * args.nsmooth * ((N >> l) - 1) ** 2 for l in range(L - 1))
-    if roof is not None and rank == 0:
+    if args.full and roof is not None and rank == 0:
         # measured ceilings (mgx_stream_bandwidth): a copy, and the smoother's
         # 4-in/1-out stream shape; hbm_frac_of_stream = measured traffic rate
         # over the latter
@@ -884,7 +934,7 @@ def main():
                    if overlap_ab else None,
                    "last_residual": res},
         "roofline": roof,
-        "gpu_state": gpu_state.report(),
+        "gpu_state": gpu_state.report() if args.full else None,
         "kernels": kernels,
         "velocity": velocity_note(fac.value, tower == pkg._lib.TOWER_CORRECT, L)
                     if world == 1 else None,
@@ -904,7 +954,7 @@ def main():
         out["host_buffers"] = pcie
     if rccl_check is not None:
         out["rccl_parity"] = rccl_check
-    if rank == 0 and world == 1 and args.cpu_baseline != "off":
+    if args.full and rank == 0 and world == 1 and args.cpu_baseline != "off":
         try:
             out["cpu_baseline"] = cpu_baseline(args)
         except Exception as e:   # the baseline is reported, never fatal

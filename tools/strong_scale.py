@@ -25,7 +25,7 @@ def main():
     import torch
     avail = torch.cuda.device_count()
     common = ["--steps", str(a.steps), "--warmup", str(a.warmup), "--N", str(a.N),
-              "--levels", str(a.levels), "--cpu-baseline", "off", "--no-profile"]
+              "--levels", str(a.levels), "--full", "--cpu-baseline", "off", "--no-profile"]
     rows = []
     for g in (int(x) for x in a.gpus.split(",")):
         if g > avail:
