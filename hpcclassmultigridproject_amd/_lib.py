@@ -100,6 +100,9 @@ _SIGS = {
     "mgx_write_uT": (_I, [C.c_char_p, _vp, _L, _L, _L, _I, _I]),
     "mgx_factor_velocity": (_I, [_vp, _L, _L, _D, _vp, _vp]),
     "mgx_velocity_factored": (_I, [_vp, C.POINTER(_I)]),
+    "mgx_factor_velocity_device": (_I, [_vp, _L, _L, _L, _D, _vp, _vp, C.POINTER(_I)]),
+    "mgx_set_velocity": (_I, [_vp, _vp, _vp]),
+    "mgx_set_velocity_device": (_I, [_vp, _vp, _vp]),
     "mgx_build_id": (C.c_char_p, []),
     "mgx_build_sources_id": (C.c_char_p, []),
 }
@@ -164,3 +167,29 @@ def stream_bandwidth(bytes_per_stream=1 << 30, nin=1, reps=10) -> float:
     g = C.c_double()
     check(lib().mgx_stream_bandwidth(bytes_per_stream, nin, reps, C.byref(g)))
     return g.value
+
+
+def factor_velocity_device(v, n, ld=None, smin=0.0):
+    """mgx_factor_velocity_device on a device tensor v (anything with
+    data_ptr() and numel(): rows x ld float64, the field in its first n+1
+    columns; ld defaults to n+1) -> (factored, a, b): a[rows], b[n+1] as numpy
+    arrays holding the bits mgx_factor_velocity returns for the same field, or
+    (False, None, None)."""
+    import numpy as np
+    import torch
+    ld = n + 1 if ld is None else ld
+    if ld < n + 1:
+        raise ValueError("ld must be >= n+1")
+    # (the last row may end after its n+1 entries)
+    rows = (v.numel() + ld - (n + 1)) // ld
+    if v.dtype != torch.float64 or not v.is_contiguous() or rows < 1:
+        raise ValueError("expected a contiguous float64 tensor of rows x ld entries")
+    a = torch.empty(rows, dtype=torch.float64, device=v.device)
+    b = torch.empty(n + 1, dtype=torch.float64, device=v.device)
+    f = C.c_int(0)
+    with torch.cuda.device(v.device):
+        check(lib().mgx_factor_velocity_device(v.data_ptr(), rows, n, ld, smin, a.data_ptr(),
+                                               b.data_ptr(), C.byref(f)))
+    if not f.value:
+        return False, None, None
+    return True, a.cpu().numpy(), b.cpu().numpy()

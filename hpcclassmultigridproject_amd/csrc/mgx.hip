@@ -19,6 +19,7 @@
 
 #include "ctx.h"
 #include "sepvel.h"
+#include "vfactor.h"
 
 namespace mgxi {
 
@@ -42,6 +43,40 @@ bool factor_velocity(const double *v1, const double *v2, long n, long r0, long r
     b2.assign(w, 0.0);
     return mgxsep::factor_rank1(v1, rows, w, w, smin, a1.data(), b1.data(), 0, js1) &&
            mgxsep::factor_rank1(v2, rows, w, w, smin, a2.data(), b2.data(), 0, js2);
+}
+
+// tuning key "device_factor": which uploads factor the velocity with the device
+// backend (vfactor.hip) on the finest level's tower copy: 1 (default) = those
+// from device pointers (the host never sees their fields), 2 = those from host
+// pointers too (after their copy), 0 = none: a device upload keeps the 2-D
+// arrays.  The same factors either way (sepvel.h decides for both backends).
+long g_device_factor = 1;
+
+// factor_velocity on the context's own copy of the finest v1 / v2; *found =
+// both fields are rank-1
+static int factor_velocity_device(mgx_ctx *c, double smin, std::vector<double> &a1,
+                                  std::vector<double> &b1, std::vector<double> &a2,
+                                  std::vector<double> &b2, bool *found) {
+    *found = false;
+    const Level &L = c->lv[0];
+    const long w = c->N + 1;
+    a1.assign(w, 0.0);
+    a2.assign(w, 0.0);
+    b1.assign(w, 0.0);
+    b2.assign(w, 0.0);
+    if (!g_sep_velocity) return MGX_OK;
+    for (int f = 0; f < 2; ++f) {
+        hipError_t e = hipSuccess;
+        const int r = mgxvf::factor_rank1_device(f ? L.v2 : L.v1, w, w, L.pitch, smin,
+                                                 (f ? a2 : a1).data(), (f ? b2 : b1).data(),
+                                                 c->stream, nullptr, &e);
+        if (r < 0)
+            return fail(MGX_E_HIP, std::string("device velocity factorisation: ") +
+                                       hipGetErrorString(e));
+        if (r == 0) return MGX_OK;
+    }
+    *found = true;
+    return MGX_OK;
 }
 
 void free_level_factors(Level &L) {
@@ -1234,6 +1269,35 @@ int mgx_destroy(mgx_ctx *c) {
 
 }  // extern "C"
 
+// Everything derived from the finest v1 / v2 (already copied into level 0, or
+// being copied on the stream): the coarse tower, its zero rows, the finest
+// factors and the generating levels.  v1 / v2: the caller's arrays (host
+// pointers for hipMemcpyHostToDevice).  Captured sub-cycles hold the old
+// velocity's vz / vgen / factor pointers in their kernel arguments, so they go.
+static int derive_velocity(mgx_ctx *c, const double *v1, const double *v2, hipMemcpyKind kind) {
+    Level &L = c->lv[0];
+    // (a replay may still be running: free_ctx drains the stream first too)
+    if (!c->graphs.empty()) HIPCHK(hipStreamSynchronize(c->stream));
+    free_graphs(c);
+    CHK(build_tower(c));
+    CHK(find_zero_rows(c));
+    // exact velocity factors for the finest level's cross pass: from the host
+    // arrays, or from the tower copy on the device ("device_factor")
+    free_level_factors(L);
+    std::vector<double> a1, b1, a2, b2;
+    const bool host = kind == hipMemcpyHostToDevice;
+    bool found = false;
+    if (c->L > 1 && c->N >= kCrossMinN) {
+        if (host ? g_device_factor == 2 : g_device_factor >= 1)
+            CHK(factor_velocity_device(c, L.coef.h * 0.5, a1, b1, a2, b2, &found));
+        else if (host)
+            found = factor_velocity(v1, v2, c->N, 0, c->N + 1, L.coef.h * 0.5, a1, b1, a2, b2);
+    }
+    if (found) CHK(set_level_factors(L, 0, a1, b1, a2, b2, c->stream));
+    CHK(find_vgen(c, a1, a2));
+    return MGX_OK;
+}
+
 int mgxi::upload_ctx(mgx_ctx *c, const double *u0, const double *v1, const double *v2,
                      hipMemcpyKind kind) {
     if (!c || !u0 || !v1 || !v2) return fail(MGX_E_ARG, "mgx_upload: bad args");
@@ -1243,6 +1307,7 @@ int mgxi::upload_ctx(mgx_ctx *c, const double *u0, const double *v1, const doubl
     L.cur = 0;
     L.zero = false;
     L.spec = -1;
+    L.xin = -1;
     c->step_spec = false;   // a pending next-step state belongs to the old fields
     const double *src[3] = {u0, v1, v2};
     double *dst[3] = {L.u[0], L.v1, L.v2};
@@ -1253,16 +1318,43 @@ int mgxi::upload_ctx(mgx_ctx *c, const double *u0, const double *v1, const doubl
         c->lv[l].cur = 0;
         c->lv[l].zero = false;
     }
-    CHK(build_tower(c));
-    CHK(find_zero_rows(c));
-    // exact velocity factors for the finest level's cross pass (host data only;
-    // a device upload keeps the 2-D arrays)
-    free_level_factors(L);
-    std::vector<double> a1, b1, a2, b2;
-    if (kind == hipMemcpyHostToDevice && c->L > 1 && c->N >= kCrossMinN &&
-        factor_velocity(v1, v2, c->N, 0, c->N + 1, L.coef.h * 0.5, a1, b1, a2, b2))
-        CHK(set_level_factors(L, 0, a1, b1, a2, b2, c->stream));
-    CHK(find_vgen(c, a1, a2));
+    CHK(derive_velocity(c, v1, v2, kind));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return MGX_OK;
+}
+
+// mgx_set_velocity: the finest u stays where it is (the buffer mgx_download
+// reads); everything computed with the old velocity is dropped.
+static int set_velocity_impl(mgx_ctx *c, const double *v1, const double *v2,
+                             hipMemcpyKind kind) {
+    if (!c || !v1 || !v2) return fail(MGX_E_ARG, "mgx_set_velocity: bad args");
+    if (c->dist)
+        return fail(MGX_E_ARG, "mgx_set_velocity: not available on a partitioned context "
+                               "(upload the new fields with mgx_upload)");
+    HIPCHK(hipSetDevice(c->device));
+    CHK(materialize(c, 0));
+    Level &L = c->lv[0];
+    // the speculative next cycle / next step, the unstored u_post's input, a
+    // deferred coarsest solve: all formed with the old velocity
+    L.spec = -1;
+    L.xin = -1;
+    c->step_spec = false;
+    c->step_next = false;
+    c->step_res0 = 0;
+    c->post_only = false;
+    c->cf_level = -1;
+    c->cf_reps = 0;
+    const size_t row = (c->N + 1) * sizeof(double);
+    const double *src[2] = {v1, v2};
+    double *dst[2] = {L.v1, L.v2};
+    for (int k = 0; k < 2; ++k)
+        HIPCHK(hipMemcpy2DAsync(dst[k], L.pitch * sizeof(double), src[k], row, row, c->N + 1,
+                                kind, c->stream));
+    for (int l = 1; l < c->L; ++l) {
+        c->lv[l].cur = 0;
+        c->lv[l].zero = false;
+    }
+    CHK(derive_velocity(c, v1, v2, kind));
     HIPCHK(hipStreamSynchronize(c->stream));
     return MGX_OK;
 }
@@ -1276,6 +1368,12 @@ int mgx_upload(mgx_ctx *c, const double *u0, const double *v1, const double *v2)
 int mgx_upload_device(mgx_ctx *c, const double *u0, const double *v1, const double *v2) {
     if (c && c->dist) return dist_upload(c, u0, v1, v2, hipMemcpyDeviceToDevice);
     return upload_ctx(c, u0, v1, v2, hipMemcpyDeviceToDevice);
+}
+int mgx_set_velocity(mgx_ctx *c, const double *v1, const double *v2) {
+    return set_velocity_impl(c, v1, v2, hipMemcpyHostToDevice);
+}
+int mgx_set_velocity_device(mgx_ctx *c, const double *v1, const double *v2) {
+    return set_velocity_impl(c, v1, v2, hipMemcpyDeviceToDevice);
 }
 
 static int download_impl(mgx_ctx *c, int level, int field, double *out, hipMemcpyKind kind) {
@@ -1665,6 +1763,27 @@ extern "C" int mgx_factor_velocity(const double *v, long rows, long n, double sm
     return mgxsep::factor_rank1(v, rows, n + 1, n + 1, smin, a, b) ? 1 : 0;
 }
 
+// The same on a field in device memory (vfactor.hip), row stride ld; a, b are
+// device pointers too.
+extern "C" int mgx_factor_velocity_device(const double *v, long rows, long n, long ld, double smin,
+                                          double *a, double *b, int *factored) {
+    if (!v || !a || !b || !factored || rows < 1 || n < 1 || ld < n + 1)
+        return fail(MGX_E_ARG, "mgx_factor_velocity_device: bad args");
+    *factored = 0;
+    std::vector<double> ha((size_t)rows), hb((size_t)n + 1);
+    hipError_t e = hipSuccess;
+    const int r = mgxvf::factor_rank1_device(v, rows, n + 1, ld, smin, ha.data(), hb.data(),
+                                             nullptr, nullptr, &e);
+    if (r < 0)
+        return fail(MGX_E_HIP, std::string("mgx_factor_velocity_device: ") + hipGetErrorString(e));
+    if (r == 1) {
+        HIPCHK(hipMemcpy(a, ha.data(), sizeof(double) * ha.size(), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(b, hb.data(), sizeof(double) * hb.size(), hipMemcpyHostToDevice));
+        *factored = 1;
+    }
+    return MGX_OK;
+}
+
 // whether the context's finest level holds velocity factors (its cross pass
 // reads rhs and u only)
 extern "C" int mgx_velocity_factored(mgx_ctx *c, int *factored) {
@@ -1793,6 +1912,11 @@ extern "C" int mgx_set_tuning(const char *key, long value) {
         mgxi::g_sep_velocity = value;
         return MGX_OK;
     }
+    if (!strcmp(key, "device_factor")) {
+        if (value < 0 || value > 2) return fail(MGX_E_ARG, "device_factor must be 0, 1 or 2");
+        mgxi::g_device_factor = value;
+        return MGX_OK;
+    }
     if (!strcmp(key, "vgen")) {
         if (value != 0 && value != 1) return fail(MGX_E_ARG, "vgen must be 0 or 1");
         mgxi::g_vgen = value;
@@ -1903,6 +2027,19 @@ extern "C" int mgx_get_tuning(const char *key, long *value) {
     }
     if (!strcmp(key, "sep_velocity")) {
         *value = mgxi::g_sep_velocity;
+        return MGX_OK;
+    }
+    if (!strcmp(key, "device_factor")) {
+        *value = mgxi::g_device_factor;
+        return MGX_OK;
+    }
+    // (read-only, for measurements: the check-kernel launches of this thread's
+    // last device factorisation and their summed device microseconds)
+    if (!strcmp(key, "vfactor_rounds") || !strcmp(key, "vfactor_us")) {
+        int rounds = 0;
+        double ms = 0;
+        mgxvf::last_stats(&rounds, &ms);
+        *value = key[8] == 'r' ? (long)rounds : (long)(ms * 1e3);
         return MGX_OK;
     }
     if (!strcmp(key, "vgen")) {

@@ -141,6 +141,23 @@ class Multigrid:
             check(lib().mgx_upload_device(self._h, u0.data_ptr(), v1.data_ptr(),
                                           v2.data_ptr()))
 
+    def set_velocity(self, v1, v2):
+        """Replace the velocity and keep the finest-level u (mgx_set_velocity):
+        the same, bit for bit, as download() + upload(u, v1, v2) without moving
+        u.  numpy arrays or device tensors in the reference layout; call rhs()
+        or step() next.  Single-GPU solvers only."""
+        if isinstance(v1, np.ndarray):
+            check(lib().mgx_set_velocity(self._h, _np_ptr(v1), _np_ptr(v2)))
+        else:
+            check(lib().mgx_set_velocity_device(self._h, v1.data_ptr(), v2.data_ptr()))
+
+    def velocity_factored(self):
+        """mgx_velocity_factored: bit 0 = the finest level keeps velocity
+        factors, bit l = level l generates its velocity from them."""
+        f = C.c_int(0)
+        check(lib().mgx_velocity_factored(self._h, C.byref(f)))
+        return f.value
+
     def dist_rows(self, part=0):
         """-> (lo, hi): allocated finest-level rows of local part `part`."""
         lo, hi = C.c_int(), C.c_int()

@@ -400,6 +400,34 @@ int mgx_write_uT(const char *path, const double *rows, long N, long r0, long r1,
  * first replicated level (maxlvl for a single-GPU context). */
 int mgx_dist_info(mgx_ctx *ctx, int *world, int *rank, int *replicated_level);
 
+/* ---- Device-resident and time-dependent velocity fields ---------------------
+ * Tuning key "device_factor": which uploads find the exact rank-1 factors of
+ * v1 / v2 ("sep_velocity") with the device verifier (csrc/vfactor.hip, part of
+ * mgx_build_sources_id) on the context's own copy of the fields: 1 (default)
+ * = uploads from device pointers (mgx_upload_device, mgx_set_velocity_device,
+ * partitioned contexts built from them), 2 = uploads from host pointers too
+ * (after their copy), 0 = none: a device upload keeps the 2-D arrays and runs
+ * the generic passes.  The host and the device backend return the same
+ * factors; u, norms and cycle counts do not depend on the key.
+ * (Read-only, mgx_get_tuning: "vfactor_rounds" / "vfactor_us" = the check-
+ * kernel launches of the calling thread's last device factorisation of one
+ * field and their summed device microseconds, for measurements.) */
+/* Device counterpart of mgx_factor_velocity: v (rows x (n+1), row stride ld
+ * doubles), a[rows], b[n+1] are DEVICE pointers; *factored = 1 and a, b filled
+ * with the same bits the host function returns for the same field, else 0.
+ * Null stream; synchronises. */
+int mgx_factor_velocity_device(const double *v, long rows, long n, long ld,
+                               double smin, double *a, double *b, int *factored);
+/* Replace the velocity of a single-GPU context and keep the finest-level u:
+ * equivalent, bit for bit in everything that follows, to downloading u and
+ * calling mgx_upload(ctx, u, v1, v2).  Host / device pointers, reference layout.
+ * The coarse velocity tower, its zero rows, the factors and the generating
+ * levels are rebuilt; the rhs, a pending next step and captured sub-cycles of
+ * the old velocity are dropped (call mgx_rhs or mgx_step next).  A partitioned
+ * context returns MGX_E_ARG. */
+int mgx_set_velocity(mgx_ctx *ctx, const double *v1, const double *v2);
+int mgx_set_velocity_device(mgx_ctx *ctx, const double *v1, const double *v2);
+
 #ifdef __cplusplus
 }
 #endif
