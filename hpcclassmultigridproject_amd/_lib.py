@@ -73,6 +73,7 @@ _SIGS = {
     "mgx_vcycle": (_I, [_vp]),
     "mgx_mg_outer": (_I, [_vp, _D, C.POINTER(_I), _dp, _dp]),
     "mgx_step": (_I, [_vp, _D, C.POINTER(_I)]),
+    "mgx_step_ex": (_I, [_vp, _D, C.POINTER(_I), _dp, _dp]),
     "mgx_run_cycles": (_I, [_vp, _I, _dp]),
     "mgx_level_n": (_I, [_vp, _I, C.POINTER(_L)]),
     "mgx_download_level": (_I, [_vp, _I, _I, _vp]),
@@ -103,6 +104,11 @@ _SIGS = {
     "mgx_factor_velocity_device": (_I, [_vp, _L, _L, _L, _D, _vp, _vp, C.POINTER(_I)]),
     "mgx_set_velocity": (_I, [_vp, _vp, _vp]),
     "mgx_set_velocity_device": (_I, [_vp, _vp, _vp]),
+    "mgx_set_source": (_I, [_vp, _vp]),
+    "mgx_set_source_device": (_I, [_vp, _vp]),
+    "mgx_set_source_scale": (_I, [_vp, _D]),
+    "mgx_source_info": (_I, [_vp, C.POINTER(_I), _dp]),
+    "mgx_compute_rhs_source": (_I, [_vp, _vp, _L, _vp, _vp, _D, _D, _D, _vp, _D]),
     "mgx_build_id": (C.c_char_p, []),
     "mgx_build_sources_id": (C.c_char_p, []),
 }
@@ -167,6 +173,20 @@ def stream_bandwidth(bytes_per_stream=1 << 30, nin=1, reps=10) -> float:
     g = C.c_double()
     check(lib().mgx_stream_bandwidth(bytes_per_stream, nin, reps, C.byref(g)))
     return g.value
+
+
+def compute_rhs_source(rhs, u, n, v1, v2, k, nu, h, f, c):
+    """mgx_compute_rhs_source: rhs = fl(compute_rhs(u) + fl(c * f)) on the
+    interior (boundary of rhs untouched).  Device tensors (float64, contiguous,
+    (n+1)^2 entries, reference layout) or raw device pointers; null stream."""
+    def ptr(x):
+        if isinstance(x, int):
+            return x
+        if x.numel() < (n + 1) * (n + 1) or not x.is_contiguous() or x.element_size() != 8:
+            raise ValueError("expected a contiguous float64 tensor of (n+1)^2 entries")
+        return x.data_ptr()
+    check(lib().mgx_compute_rhs_source(ptr(rhs), ptr(u), n, ptr(v1), ptr(v2), k, nu, h, ptr(f),
+                                       c))
 
 
 def factor_velocity_device(v, n, ld=None, smin=0.0):

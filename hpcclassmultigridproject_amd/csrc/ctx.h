@@ -88,6 +88,13 @@ struct mgx_ctx {
     double *stage[2] = {nullptr, nullptr};   // reference-layout (N+1)^2 staging
     double *zrow = nullptr;   // one row of zeros (finest pitch): Level::vz rows read it
     double2 *vga = nullptr;   // VGen::a of the Level::vgen levels, N+2 pairs
+    // mgx_set_source: the context's own pitched copy of f (finest level, tower
+    // layout), or null = the homogeneous equation; every finest compute_rhs
+    // adds fl(fl(dt * src_scale) * f) through csrc/source.hip.  A partitioned
+    // context keeps the copies in its parts (dist.hip) and src_active here.
+    double *src = nullptr;
+    double src_scale = 1.0;
+    bool src_active = false;
     mgxi::Dist *dist = nullptr;   // row-partitioned multi-GPU state (dist.hip)
     // mg_outer's cycle predicted to be the last: its finest level runs the
     // post-smoothing alone, not the cross pass (no next-cycle pre-smoothing)
@@ -189,6 +196,13 @@ int create_ctx(mgx_ctx **out, long n, int maxlvl, double dt, double nu, const mg
                hipStream_t stream);
 int upload_ctx(mgx_ctx *c, const double *u0, const double *v1, const double *v2,
                hipMemcpyKind kind);
+// mgx_set_source on a single-GPU context (f == nullptr removes it); every
+// state formed from the old right-hand side is dropped
+int set_source_ctx(mgx_ctx *c, const double *f, hipMemcpyKind kind);
+void drop_source_state(mgx_ctx *c);
+// tuning key "source_sv" (mgx.hip): the source pass reads the finest level's
+// velocity factors, where the context keeps them, instead of the 2-D v1 / v2
+extern long g_source_sv;
 
 // dist.hip entry points used by the C ABI
 int dist_upload(mgx_ctx *c, const double *u0, const double *v1, const double *v2,
@@ -198,6 +212,10 @@ int dist_owned_rows(mgx_ctx *c, int part, int *ra, int *rb);
 int dist_download_rows(mgx_ctx *c, int part, double *out, hipMemcpyKind kind);
 int dist_rhs(mgx_ctx *c);
 int dist_rhs_norm(mgx_ctx *c, double *res0);
+// whole-grid source (reference layout): every part keeps its owned rows, the
+// replicated sub-contexts of a fully replicated context the whole field
+int dist_set_source(mgx_ctx *c, const double *f, hipMemcpyKind kind);
+void dist_set_source_scale(mgx_ctx *c, double s);
 int dist_vcycle(mgx_ctx *c, double *norm, bool store_post = true);
 // partitioned level 0 runs the cross-cycle pass; recompute its unstored u_post
 bool dist_post_predictable(mgx_ctx *c);

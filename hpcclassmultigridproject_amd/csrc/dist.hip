@@ -35,6 +35,7 @@
 
 #include "ctx.h"
 #include "plan.h"
+#include "source.h"
 
 namespace mgxi {
 
@@ -108,6 +109,9 @@ struct PLevel {
     int xin = -1;    // level 0: input buffer of the last cross-cycle pass (Level::xin)
     bool zero = false;
     double *rhs = nullptr, *v1 = nullptr, *v2 = nullptr;
+    // level 0: this part's owned rows [ra, rb) of the source (mgx_set_source),
+    // pitched, or null
+    double *src = nullptr;
     // level 0: exact velocity factors (sepvel.h) indexed by GLOBAL row / column
     // (full-length arrays, this block's rows filled), or null
     double *sa1 = nullptr, *sb1 = nullptr, *sa2 = nullptr, *sb2 = nullptr;
@@ -190,6 +194,7 @@ void dist_free(mgx_ctx *c) {
             (void)hipFree(L.rhs);
             (void)hipFree(L.v1);
             (void)hipFree(L.v2);
+            (void)hipFree(L.src);
             for (double *f : {L.sa1, L.sb1, L.sa2, L.sb2}) (void)hipFree(f);
         }
         if (p.sub) free_ctx(p.sub);
@@ -1002,6 +1007,39 @@ int dist_residual_norm(mgx_ctx *c, double *norm) {
     return reduce_norm(c, norm);
 }
 
+// The source pass (source.hip) on a part's owned rows of level 0: the rhs of
+// rows [ra, rb), for dist_rhs_norm also the part's sum of squares into
+// p.dsum.  The term is pointwise: the kRhs exchange that follows carries it.
+static mgxsrc::SrcArgs source_args(mgx_ctx *c, Part &p, bool norm, double *cbytes) {
+    PLevel &L = p.lv[0];
+    mgxsrc::SrcArgs A;
+    A.rhs = L.F(L.rhs);
+    A.u = L.U();
+    A.v1 = L.F(L.v1);
+    A.v2 = L.F(L.v2);
+    A.f = L.src - (long)L.ra * L.pitch;   // + r*pitch = global row r, r in [ra, rb)
+    A.cf = c->dt * c->src_scale;
+    A.n = L.n;
+    A.pitch = L.pitch;
+    A.c = L.coef;
+    A.ra = L.ra;
+    A.rb = L.rb;
+    const bool sv = g_source_sv != 0 && L.sa1 && L.sb1 && L.sa2 && L.sb2;
+    if (sv) {
+        A.sa1 = L.sa1;
+        A.sb1 = L.sb1;
+        A.sa2 = L.sa2;
+        A.sb2 = L.sb2;
+    }
+    if (norm) {
+        A.partials = p.partials;
+        A.norm_out = p.dsum;
+        A.take_sqrt = false;
+    }
+    *cbytes = (sv ? 24.0 : 40.0) * L.Mown();
+    return A;
+}
+
 int dist_rhs(mgx_ctx *c) {
     Dist *d = c->dist;
     HIPCHK(hipSetDevice(c->device));
@@ -1014,6 +1052,13 @@ int dist_rhs(mgx_ctx *c) {
     CHK(xchg(c, 0, kU));
     for (auto &p : d->parts) {
         PLevel &L = p.lv[0];
+        if (L.src) {
+            double cb = 0;
+            const mgxsrc::SrcArgs A = source_args(c, p, false, &cb);
+            CHK(launch(c, MGX_K_RHS, 0, 40.0 * L.Mown(), cb,
+                       [&] { mgxsrc::launch_rhs_source(A, c->stream); }));
+            continue;
+        }
         CHK(launch(c, MGX_K_RHS, 0, 32.0 * L.Mown(), [&] {
             mgx::launch_rhs(L.F(L.rhs), L.U(), L.F(L.v1), L.F(L.v2), L.n, L.pitch, L.coef,
                             c->stream, L.ra, L.rb);
@@ -1036,6 +1081,13 @@ int dist_rhs_norm(mgx_ctx *c, double *res0) {
     CHK(xchg(c, 0, kU));
     for (auto &p : d->parts) {
         PLevel &L = p.lv[0];
+        if (L.src) {
+            double cb = 0;
+            const mgxsrc::SrcArgs A = source_args(c, p, true, &cb);
+            CHK(launch(c, MGX_K_RHS, 0, 88.0 * L.Mown(), cb,
+                       [&] { mgxsrc::launch_rhs_source(A, c->stream); }));
+            continue;
+        }
         CHK(launch(c, MGX_K_RHS, 0, 80.0 * L.Mown(), 32.0 * L.Mown(), [&] {
             mgx::launch_rhs_norm(L.F(L.rhs), L.U(), L.F(L.v1), L.F(L.v2), L.n, L.pitch, L.coef,
                                  p.partials, p.dsum, c->stream, L.ra, L.rb,
@@ -1044,6 +1096,84 @@ int dist_rhs_norm(mgx_ctx *c, double *res0) {
     }
     CHK(xchg(c, 0, kRhs));
     return reduce_norm(c, res0);
+}
+
+// mgx_set_source on a partitioned context: f is the whole grid (reference
+// layout, host or device).  A part keeps its owned rows; with every level
+// replicated (la == 0) the rhs runs through the sub-contexts, so each of them
+// keeps the whole field.  f == nullptr removes it.
+static void free_sources(mgx_ctx *c) {
+    for (auto &p : c->dist->parts) {
+        if (!p.lv.empty()) {
+            (void)hipFree(p.lv[0].src);
+            p.lv[0].src = nullptr;
+        }
+    }
+    c->src_active = false;
+}
+int dist_set_source(mgx_ctx *c, const double *f, hipMemcpyKind kind) {
+    Dist *d = c->dist;
+    HIPCHK(hipSetDevice(c->device));
+    CHK(settle(c));
+    dist_set_source_scale(c, c->src_scale);   // drops the speculative states
+    if (d->la == 0) {
+        int rc = MGX_OK;
+        for (auto &p : d->parts)
+            if (rc == MGX_OK) rc = set_source_ctx(p.sub, f, kind);
+        if (rc != MGX_OK)   // all parts or none
+            for (auto &p : d->parts) (void)set_source_ctx(p.sub, nullptr, kind);
+        c->src_active = rc == MGX_OK && f;
+        return rc;
+    }
+    if (!f) {
+        HIPCHK(hipStreamSynchronize(c->stream));   // a pass may still read the copies
+        free_sources(c);
+        return MGX_OK;
+    }
+    const size_t row = (c->N + 1) * sizeof(double);
+    auto copy_all = [&]() -> int {
+        for (auto &p : d->parts) {
+            PLevel &L = p.lv[0];
+            const size_t bytes = sizeof(double) * (size_t)(L.rb - L.ra) * (size_t)L.pitch;
+            if (!L.src) {
+                const hipError_t e = hipMalloc(&L.src, bytes);
+                if (e != hipSuccess) {
+                    (void)hipGetLastError();
+                    L.src = nullptr;
+                    return fail(MGX_E_HIP, std::string("mgx_set_source: no room for the part's "
+                                                       "rows of the source: ") +
+                                               hipGetErrorString(e));
+                }
+                HIPCHK(hipMemsetAsync(L.src, 0, bytes, c->stream));
+            }
+            HIPCHK(hipMemcpy2DAsync(L.src, L.pitch * sizeof(double),
+                                    f + (long)L.ra * (c->N + 1), row, row, L.rb - L.ra, kind,
+                                    c->stream));
+        }
+        HIPCHK(hipStreamSynchronize(c->stream));   // the caller's buffer is free on return
+        return MGX_OK;
+    };
+    const int rc = copy_all();
+    if (rc != MGX_OK) {   // all parts or none
+        (void)hipStreamSynchronize(c->stream);
+        free_sources(c);
+        return rc;
+    }
+    c->src_active = true;
+    return MGX_OK;
+}
+void dist_set_source_scale(mgx_ctx *c, double s) {
+    for (auto &p : c->dist->parts) {
+        if (!p.lv.empty()) {
+            p.lv[0].spec = -1;
+            p.lv[0].xin = -1;
+        }
+        if (p.sub) {
+            drop_source_state(p.sub);
+            p.sub->src_scale = s;
+        }
+    }
+    drop_source_state(c);
 }
 
 // mgx_synchronize of a partitioned context: the side stream's pending

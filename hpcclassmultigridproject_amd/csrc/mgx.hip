@@ -19,6 +19,7 @@
 
 #include "ctx.h"
 #include "sepvel.h"
+#include "source.h"
 #include "vfactor.h"
 
 namespace mgxi {
@@ -748,10 +749,52 @@ int op_vcycle(mgx_ctx *c, int l, double *norm, bool store_post) {
     return MGX_OK;
 }
 
+// tuning key "source_sv": 1 (default) = the source pass of a context that keeps
+// finest-level velocity factors forms v1, v2 from them; 0 = always reads the
+// 2-D arrays (bitwise the same)
+long g_source_sv = 1;
+
+// The source pass (source.hip) on a single-GPU context's finest level; the
+// factor variant is chosen per launch (a velocity replacement can add or
+// remove the factors).  norm: also the residual norm against the new rhs into
+// c->dscal[0].  *cbytes: the arrays the launch reads or writes, once.
+static mgxsrc::SrcArgs source_args(mgx_ctx *c, bool norm, double *cbytes) {
+    Level &L = c->lv[0];
+    mgxsrc::SrcArgs A;
+    A.rhs = L.rhs;
+    A.u = L.U();
+    A.v1 = L.v1;
+    A.v2 = L.v2;
+    A.f = c->src;
+    A.cf = c->dt * c->src_scale;
+    A.n = L.n;
+    A.pitch = L.pitch;
+    A.c = L.coef;
+    const bool sv = g_source_sv != 0 && L.sa1 && L.sb1 && L.sa2 && L.sb2;
+    if (sv) {
+        A.sa1 = L.sa1;
+        A.sb1 = L.sb1;
+        A.sa2 = L.sa2;
+        A.sb2 = L.sb2;
+    }
+    if (norm) {
+        A.partials = c->partials;
+        A.norm_out = c->dscal;
+    }
+    *cbytes = (sv ? 24.0 : 40.0) * L.M();   // u, f, rhs (+ v1, v2)
+    return A;
+}
+
 int op_rhs(mgx_ctx *c) {
     drop_spec(c);
     CHK(materialize(c, 0));
     Level &L = c->lv[0];
+    if (c->src) {   // compute_rhs 32 B per point + the f stream
+        double cb = 0;
+        const mgxsrc::SrcArgs A = source_args(c, false, &cb);
+        return launch(c, MGX_K_RHS, 0, 40.0 * L.M(), cb,
+                      [&] { mgxsrc::launch_rhs_source(A, c->stream); });
+    }
     return launch(c, MGX_K_RHS, 0, 32.0 * L.M(), [&] {
         mgx::launch_rhs(L.rhs, L.U(), L.v1, L.v2, L.n, L.pitch, L.coef, c->stream);
     });
@@ -763,6 +806,13 @@ static int op_rhs_norm(mgx_ctx *c, double *res0) {
     drop_spec(c);
     CHK(materialize(c, 0));
     Level &L = c->lv[0];
+    if (c->src) {
+        double cb = 0;
+        const mgxsrc::SrcArgs A = source_args(c, true, &cb);
+        CHK(launch(c, MGX_K_RHS, 0, 40.0 * L.M() + 48.0 * L.M(), cb,
+                   [&] { mgxsrc::launch_rhs_source(A, c->stream); }));
+        return read_norm(c, res0);
+    }
     CHK(launch(c, MGX_K_RHS, 0, 32.0 * L.M() + 48.0 * L.M(), 32.0 * L.M(), [&] {
         mgx::launch_rhs_norm(L.rhs, L.U(), L.v1, L.v2, L.n, L.pitch, L.coef, c->partials,
                              c->dscal, c->stream);
@@ -1071,6 +1121,7 @@ void free_ctx(mgx_ctx *c) {
     (void)hipFree(c->stage[1]);
     (void)hipFree(c->zrow);
     (void)hipFree(c->vga);
+    (void)hipFree(c->src);
     if (c->hscal) (void)hipHostFree(c->hscal);
     for (auto &r : c->pending) {
         (void)hipEventDestroy(r.e0);
@@ -1359,7 +1410,93 @@ static int set_velocity_impl(mgx_ctx *c, const double *v1, const double *v2,
     return MGX_OK;
 }
 
+// Whatever was formed from the old right-hand side goes: the speculative next
+// cycle / next step (made with the old rhs), the unstored u_post's input.  The
+// finest u stays where it is, as in set_velocity_impl.
+void mgxi::drop_source_state(mgx_ctx *c) {
+    drop_spec(c);
+    if (!c->lv.empty()) c->lv[0].xin = -1;
+    c->step_next = false;
+    c->step_res0 = 0;
+    c->post_only = false;
+}
+
+// mgx_set_source on a single-GPU context: the context's own pitched copy of f
+// (allocated on the first call, reused by a replacement), or none.
+int mgxi::set_source_ctx(mgx_ctx *c, const double *f, hipMemcpyKind kind) {
+    HIPCHK(hipSetDevice(c->device));
+    drop_source_state(c);
+    Level &L = c->lv[0];
+    if (!f) {
+        if (c->src) {
+            HIPCHK(hipStreamSynchronize(c->stream));   // a pass may still read it
+            (void)hipFree(c->src);
+            c->src = nullptr;
+        }
+        c->src_active = false;
+        return MGX_OK;
+    }
+    const size_t bytes = sizeof(double) * (size_t)(L.n + 1) * (size_t)L.pitch;
+    if (!c->src) {
+        const hipError_t e = hipMalloc(&c->src, bytes);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            c->src = nullptr;
+            c->src_active = false;
+            return fail(MGX_E_HIP, std::string("mgx_set_source: no room for the context's copy "
+                                               "of the source (one finest-level array): ") +
+                                       hipGetErrorString(e));
+        }
+        // (the pad columns are never read past column n; zero all the same)
+        HIPCHK(hipMemsetAsync(c->src, 0, bytes, c->stream));
+    }
+    const size_t row = (c->N + 1) * sizeof(double);
+    HIPCHK(hipMemcpy2DAsync(c->src, L.pitch * sizeof(double), f, row, row, c->N + 1, kind,
+                            c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));   // the caller's buffer is free on return
+    c->src_active = true;
+    return MGX_OK;
+}
+
+static int set_source_impl(mgx_ctx *c, const double *f, hipMemcpyKind kind, const char *who) {
+    if (!c) return fail(MGX_E_ARG, std::string(who) + ": null ctx");
+    if (c->dist) return dist_set_source(c, f, kind);
+    return set_source_ctx(c, f, kind);
+}
+
 extern "C" {
+
+int mgx_set_source(mgx_ctx *c, const double *f) {
+    return set_source_impl(c, f, hipMemcpyHostToDevice, "mgx_set_source");
+}
+int mgx_set_source_device(mgx_ctx *c, const double *f) {
+    return set_source_impl(c, f, hipMemcpyDeviceToDevice, "mgx_set_source_device");
+}
+int mgx_set_source_scale(mgx_ctx *c, double s) {
+    if (!c) return fail(MGX_E_ARG, "mgx_set_source_scale: null ctx");
+    if (c->dist) {
+        HIPCHK(hipSetDevice(c->device));
+        dist_set_source_scale(c, s);
+    } else {
+        drop_source_state(c);
+    }
+    c->src_scale = s;
+    return MGX_OK;
+}
+int mgx_source_info(mgx_ctx *c, int *active, double *scale) {
+    if (!c) return fail(MGX_E_ARG, "mgx_source_info: null ctx");
+    if (active) *active = c->src_active ? 1 : 0;
+    if (scale) *scale = c->src_scale;
+    return MGX_OK;
+}
+int mgx_compute_rhs_source(double *rhs, const double *u, long n, const double *v1,
+                           const double *v2, double k, double nu, double h, const double *f,
+                           double cf) {
+    if (!rhs || !u || !v1 || !v2 || !f || n < 2)
+        return fail(MGX_E_ARG, "mgx_compute_rhs_source: bad args");
+    mgxsrc::launch_raw_rhs_source(rhs, u, v1, v2, f, cf, n, mgx::make_coef(k, nu, h), nullptr);
+    return check_launch("mgx_compute_rhs_source");
+}
 
 int mgx_upload(mgx_ctx *c, const double *u0, const double *v1, const double *v2) {
     if (c && c->dist) return dist_upload(c, u0, v1, v2, hipMemcpyHostToDevice);
@@ -1499,7 +1636,8 @@ static bool step_rhs_alt(mgx_ctx *c) {
     return true;
 }
 
-static int step_impl(mgx_ctx *c, double tol, int *cycles, bool prepare_next) {
+static int step_impl(mgx_ctx *c, double tol, int *cycles, bool prepare_next,
+                     double *res0_out = nullptr, double *res_out = nullptr) {
     // compute_rhs and mg_outer's initial norm in one pass (timestepper,
     // multigrid.cpp:168-170), with the first pre-smoothing where it fuses --
     // or already done by the previous step's last cross pass
@@ -1511,19 +1649,26 @@ static int step_impl(mgx_ctx *c, double tol, int *cycles, bool prepare_next) {
         c->step_spec = false;   // lv[0].spec and lv[1]'s rhs stay: the first cycle's
     } else if (c->dist) {
         CHK(dist_rhs_norm(c, &res0));
-    } else if (step_fusable(c)) {
+    } else if (!c->src && step_fusable(c)) {
         CHK(op_rhs_norm_pre(c, &res0));
     } else {
         CHK(op_rhs_norm(c, &res0));
     }
-    c->step_next = prepare_next && g_step_cross != 0 && !c->dist && step_rhs_alt(c);
-    const int rc = op_mg_outer(c, tol, cycles, nullptr, nullptr, &res0);
+    // (a source: both fused forms make the rhs inside kernels that know none --
+    // k_wsmooth's kModeRhsNorm above, the cross pass's step mode here)
+    c->step_next =
+        prepare_next && g_step_cross != 0 && !c->dist && !c->src && step_rhs_alt(c);
+    const int rc = op_mg_outer(c, tol, cycles, res0_out, res_out, &res0);
     c->step_next = false;
     return rc;
 }
 int mgx_step(mgx_ctx *c, double tol, int *cycles) {
     if (!c) return fail(MGX_E_ARG, "null ctx");
     return step_impl(c, tol, cycles, true);
+}
+int mgx_step_ex(mgx_ctx *c, double tol, int *cycles, double *res0, double *res) {
+    if (!c) return fail(MGX_E_ARG, "mgx_step_ex: null ctx");
+    return step_impl(c, tol, cycles, true, res0, res);
 }
 int mgx_run_cycles(mgx_ctx *c, int cycles, double *res) {
     if (!c || cycles < 0) return fail(MGX_E_ARG, "mgx_run_cycles: bad args");
@@ -1922,6 +2067,11 @@ extern "C" int mgx_set_tuning(const char *key, long value) {
         mgxi::g_vgen = value;
         return MGX_OK;
     }
+    if (!strcmp(key, "source_sv")) {
+        if (value != 0 && value != 1) return fail(MGX_E_ARG, "source_sv must be 0 or 1");
+        mgxi::g_source_sv = value;
+        return MGX_OK;
+    }
     if (!strcmp(key, "zero_rows")) {
         if (value != 0 && value != 1) return fail(MGX_E_ARG, "zero_rows must be 0 or 1");
         mgxi::g_zero_rows = value;
@@ -2044,6 +2194,10 @@ extern "C" int mgx_get_tuning(const char *key, long *value) {
     }
     if (!strcmp(key, "vgen")) {
         *value = mgxi::g_vgen;
+        return MGX_OK;
+    }
+    if (!strcmp(key, "source_sv")) {
+        *value = mgxi::g_source_sv;
         return MGX_OK;
     }
     if (!strcmp(key, "zero_rows")) {

@@ -151,6 +151,35 @@ class Multigrid:
         else:
             check(lib().mgx_set_velocity_device(self._h, v1.data_ptr(), v2.data_ptr()))
 
+    def set_source(self, f):
+        """Source term of u_t + v.grad u = nu lap u + f (mgx_set_source): every
+        rhs() and step() from now on adds fl(fl(dt * scale) * f) to the
+        interior of the right-hand side.  f: a numpy array or a device tensor
+        in the reference layout ((N+1)^2 float64; the solver keeps its own
+        copy), or None to remove the source.  Survives upload() and
+        set_velocity(); call rhs() or step() next."""
+        if f is None:
+            check(lib().mgx_set_source(self._h, None))
+        elif isinstance(f, np.ndarray):
+            if f.size != (self.N + 1) ** 2:
+                raise ValueError("f must hold (N+1)^2 doubles")
+            check(lib().mgx_set_source(self._h, _np_ptr(f)))
+        else:
+            if f.numel() != (self.N + 1) ** 2 or f.element_size() != 8 or not f.is_contiguous():
+                raise ValueError("f must be a contiguous float64 tensor of (N+1)^2 entries")
+            check(lib().mgx_set_source_device(self._h, f.data_ptr()))
+
+    def set_source_scale(self, s):
+        """The factor s of the source term fl(dt * s) * f (default 1): a
+        time-separable source g(t) f(x, y) needs no new upload per step."""
+        check(lib().mgx_set_source_scale(self._h, float(s)))
+
+    def source_info(self):
+        """-> (active, scale) (mgx_source_info)."""
+        a, s = C.c_int(), C.c_double()
+        check(lib().mgx_source_info(self._h, C.byref(a), C.byref(s)))
+        return bool(a.value), s.value
+
     def velocity_factored(self):
         """mgx_velocity_factored: bit 0 = the finest level keeps velocity
         factors, bit l = level l generates its velocity from them."""
@@ -241,6 +270,14 @@ class Multigrid:
         cyc = C.c_int()
         check(lib().mgx_step(self._h, tol, C.byref(cyc)), allow=(_lib.MGX_E_NOCONV,))
         return cyc.value
+
+    def step_ex(self, tol=1e-6):
+        """step() -> (cycles, res0, res): with mg_outer's initial and last
+        residual norm (mgx_step_ex)."""
+        cyc, r0, r = C.c_int(), C.c_double(), C.c_double()
+        check(lib().mgx_step_ex(self._h, tol, C.byref(cyc), C.byref(r0), C.byref(r)),
+              allow=(_lib.MGX_E_NOCONV,))
+        return cyc.value, r0.value, r.value
 
     def run_cycles(self, cycles):
         r = C.c_double()

@@ -161,6 +161,10 @@ int mgx_vcycle(mgx_ctx *ctx);
 int mgx_mg_outer(mgx_ctx *ctx, double tol, int *cycles, double *res0, double *res);
 /* One timestep: mgx_rhs + mgx_mg_outer (multigrid.cpp:165-172). */
 int mgx_step(mgx_ctx *ctx, double tol, int *cycles);
+/* The same step; *res0 / *res (may be NULL) also receive mg_outer's initial and
+ * last residual norm, as mgx_mg_outer returns them (the initial one is taken
+ * by the pass that forms the right-hand side). */
+int mgx_step_ex(mgx_ctx *ctx, double tol, int *cycles, double *res0, double *res);
 /* Bench step x `cycles`: V-cycle + residual + norm, no tolerance stop.
  * *res (may be NULL) receives the last residual norm. */
 int mgx_run_cycles(mgx_ctx *ctx, int cycles, double *res);
@@ -427,6 +431,66 @@ int mgx_factor_velocity_device(const double *v, long rows, long n, long ld,
  * context returns MGX_E_ARG. */
 int mgx_set_velocity(mgx_ctx *ctx, const double *v1, const double *v2);
 int mgx_set_velocity_device(mgx_ctx *ctx, const double *v1, const double *v2);
+
+/* ---- Source term: u_t + v.grad u = nu lap u + f -----------------------------
+ * With a source f and a scale s (default 1) set on a context, every
+ * finest-level compute_rhs of that context -- mgx_rhs and the start of
+ * mgx_step -- gives at every interior point
+ *     rhs(i,j) = fl( Bu(i,j) + fl( c * f(i,j) ) ),   c = fl(dt * s),
+ * Bu being exactly what compute_rhs gives without a source (gs.cpp:24-53); no
+ * contraction in either fp_mode, boundary entries untouched.  f has the
+ * reference layout ((n+1)^2 row-major); its boundary entries are ignored.  For
+ * second-order Crank-Nicolson pass f at the half step: which f is the
+ * caller's business.  Everything else on such a context, everything on a
+ * context without a source, mgx_timestepper[_ex] and mgx_compute_rhs are
+ * unchanged.
+ *
+ * mgx_set_source takes a host pointer, mgx_set_source_device a device pointer.
+ * The context keeps its own pitched copy (one more finest-level array): the
+ * caller's buffer is free on return, with the ordering rules of
+ * mgx_upload[_device].  f == NULL removes the source and frees the copy: from
+ * the next call on the context behaves, bit for bit and pass for pass, as if
+ * none had ever been set.  When the copy cannot be allocated (N=65536 on one
+ * GPU has no room for another finest-level array) the call returns MGX_E_HIP
+ * with a message and leaves the context without a source.
+ * mgx_set_source_scale sets s: a time-separable source g(t) f(x,y) costs
+ * nothing per step beyond the call.  The source and the scale survive
+ * mgx_upload* and mgx_set_velocity*; only NULL or mgx_destroy removes the
+ * source.  Setting, replacing, rescaling or removing it drops whatever was
+ * formed from the old right-hand side (a pending next step, a speculative
+ * pre-smoothed u), as mgx_set_velocity does: call mgx_rhs or mgx_step next.
+ *
+ * The pass (csrc/source.hip, part of mgx_build_sources_id; profile kind
+ * MGX_K_RHS) is one row march that reads u, v1, v2 and f and writes rhs, for
+ * mgx_step also mg_outer's initial norm -- bitwise what mgx_rhs followed by
+ * mgx_residual_norm(ctx, 0) gives.  Tuning key "source_sv": 1 (default) = on a
+ * context that keeps finest-level velocity factors (bit 0 of
+ * mgx_velocity_factored) the pass forms v1, v2 from them instead of reading
+ * the 2-D arrays (three full streams instead of five; bitwise the same); 0 =
+ * always the 2-D arrays.
+ * Cost: while a source is set, mgx_step does not fuse the right-hand side into
+ * the first pre-smoothing pass ("step_fuse") or into the previous step's last
+ * cross-cycle pass ("step_cross"), which form it inside kernels that know no
+ * source; every step starts with the pass above.  The cycles themselves
+ * (cross_cycle included) are unchanged.  Measured on one MI355X (DESIGN.md
+ * section 9): a source costs about 2.9 ms per step at N=16384, L=9, fma (11.1
+ * against 8.2 ms, three cycles per step; 3.7 ms with "source_sv" 0).
+ *
+ * Partitioned contexts (mgx_create_local_dist, mgx_create_dist) take the
+ * whole-grid calls: each part keeps its owned rows, and no exchange is added
+ * (the term is pointwise).  A row-block counterpart for contexts filled with
+ * mgx_upload_rows (no rank holds the whole grid) does not exist yet. */
+int mgx_set_source(mgx_ctx *ctx, const double *f);
+int mgx_set_source_device(mgx_ctx *ctx, const double *f);
+int mgx_set_source_scale(mgx_ctx *ctx, double s);
+/* *active = 1 while a source is set, *scale = s (either may be NULL). */
+int mgx_source_info(mgx_ctx *ctx, int *active, double *scale);
+/* The gs.h-style raw op: rhs = fl(compute_rhs(u) + fl(c * f)) on the interior,
+ * device pointers in the reference layout, null stream (as mgx_compute_rhs);
+ * c is the factor itself (a context passes fl(dt * s)). */
+int mgx_compute_rhs_source(double *rhs, const double *u, long n, const double *v1,
+                           const double *v2, double k, double nu, double h, const double *f,
+                           double c);
 
 #ifdef __cplusplus
 }
