@@ -39,6 +39,20 @@ class Options(C.Structure):
                 ("fp_mode", C.c_int)]
 
 
+class Stats(C.Structure):
+    """mgx_stats (include/mgx.h): 12 eight-byte fields."""
+    _fields_ = [("count", C.c_long), ("nonfinite", C.c_long), ("sum", C.c_double),
+                ("sum_abs", C.c_double), ("sum_sq", C.c_double), ("min", C.c_double),
+                ("max", C.c_double), ("min_i", C.c_long), ("min_j", C.c_long),
+                ("max_i", C.c_long), ("max_j", C.c_long)]
+
+    def astuple(self):
+        return tuple(getattr(self, f) for f, _ in self._fields_)
+
+    def __repr__(self):
+        return "Stats(" + ", ".join(f"{f}={getattr(self, f)!r}" for f, _ in self._fields_) + ")"
+
+
 _dp = C.POINTER(C.c_double)
 _vp = C.c_void_p
 _L, _I, _D = C.c_long, C.c_int, C.c_double
@@ -109,6 +123,13 @@ _SIGS = {
     "mgx_set_source_scale": (_I, [_vp, _D]),
     "mgx_source_info": (_I, [_vp, C.POINTER(_I), _dp]),
     "mgx_compute_rhs_source": (_I, [_vp, _vp, _L, _vp, _vp, _D, _D, _D, _vp, _D]),
+    "mgx_array_stats": (_I, [_vp, _vp, _L, _I, C.POINTER(Stats)]),
+    "mgx_field_stats": (_I, [_vp, _I, _I, _I, _vp, C.POINTER(Stats)]),
+    "mgx_field_stats_rows": (_I, [_vp, _I, _I, _I, _vp, C.POINTER(Stats)]),
+    "mgx_stats_merge": (_I, [C.POINTER(Stats), C.POINTER(Stats)]),
+    "mgx_sample": (_I, [_vp, _I, _I, _L, _vp]),
+    "mgx_sample_device": (_I, [_vp, _I, _I, _L, _vp]),
+    "mgx_sample_rows": (_I, [_vp, _I, _I, _L, _vp, C.POINTER(_L), C.POINTER(_L)]),
     "mgx_build_id": (C.c_char_p, []),
     "mgx_build_sources_id": (C.c_char_p, []),
 }
@@ -187,6 +208,36 @@ def compute_rhs_source(rhs, u, n, v1, v2, k, nu, h, f, c):
         return x.data_ptr()
     check(lib().mgx_compute_rhs_source(ptr(rhs), ptr(u), n, ptr(v1), ptr(v2), k, nu, h, ptr(f),
                                        c))
+
+
+def device_ptr(x, count, what="tensor"):
+    """The device pointer of a contiguous float64 tensor of >= count entries
+    (or a raw pointer passed as an int); None stays None."""
+    if x is None or isinstance(x, int):
+        return x
+    if x.numel() < count or not x.is_contiguous() or x.element_size() != 8:
+        raise ValueError(f"{what}: expected a contiguous float64 tensor of {count} entries")
+    return x.data_ptr()
+
+
+def array_stats(a, n, interior=False, minus=None) -> Stats:
+    """mgx_array_stats: the statistics of a device array in the reference
+    layout ((n+1)^2 float64, any n >= 1), or of fl(a - minus) point by point;
+    interior: rows and columns 1..n-1 only.  Null stream; synchronises."""
+    cnt = (n + 1) * (n + 1)
+    s = Stats()
+    check(lib().mgx_array_stats(device_ptr(a, cnt, "a"), device_ptr(minus, cnt, "minus"), n,
+                                int(bool(interior)), C.byref(s)))
+    return s
+
+
+def stats_merge(a: Stats, b: Stats) -> Stats:
+    """mgx_stats_merge: the record of the union of two disjoint sets of points
+    (host only); neither argument is changed."""
+    out = Stats.from_buffer_copy(a)
+    other = Stats.from_buffer_copy(b)
+    check(lib().mgx_stats_merge(C.byref(out), C.byref(other)))
+    return out
 
 
 def factor_velocity_device(v, n, ld=None, smin=0.0):

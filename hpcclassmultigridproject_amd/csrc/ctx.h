@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/mgx.h"
+#include "diag.h"
 #include "kernels.h"
 
 namespace mgxi {
@@ -95,6 +96,9 @@ struct mgx_ctx {
     double *src = nullptr;
     double src_scale = 1.0;
     bool src_active = false;
+    // scratch of the field diagnostics (diag.h: partial records + the result),
+    // allocated by the first statistics call
+    void *diag = nullptr;
     mgxi::Dist *dist = nullptr;   // row-partitioned multi-GPU state (dist.hip)
     // mg_outer's cycle predicted to be the last: its finest level runs the
     // post-smoothing alone, not the cross pass (no next-cycle pre-smoothing)
@@ -204,12 +208,45 @@ void drop_source_state(mgx_ctx *c);
 // velocity factors, where the context keeps them, instead of the 2-D v1 / v2
 extern long g_source_sv;
 
+// Field diagnostics (mgx.hip; csrc/diag.hip), shared with dist.hip.
+// The statistics of rows [r0, r1) of a field on c's stream and scratch;
+// interior: rows and columns 1..n-1 only; minus (reference layout, or null)
+// holds rows from minus_row0 on.  Synchronises the stream.
+int stats_view(mgx_ctx *c, const mgxdiag::View &f, long r0, long r1, int interior,
+               const double *minus, long minus_row0, mgx_stats *out);
+// sampled rows A in [A0, A1) (fine rows A * stride) of a field
+struct SamplePiece {
+    mgxdiag::View f;
+    long A0 = 0, A1 = 0;
+};
+// out[(A - A0) * (n/stride + 1) + B] for the pieces' rows, `rows` rows in all:
+// gathered into a compact device buffer and copied (host out), or written by
+// the kernel (device out).  Synchronises the stream.
+int sample_pieces(mgx_ctx *c, const std::vector<SamplePiece> &pieces, long stride, long A0,
+                  long rows, double *out, bool device_out);
+// the field mgx_download_level(level, field) copies (4 = the source copy) of a
+// single-GPU context
+int field_view(mgx_ctx *c, int level, int field, mgxdiag::View *v);
+
 // dist.hip entry points used by the C ABI
 int dist_upload(mgx_ctx *c, const double *u0, const double *v1, const double *v2,
                 hipMemcpyKind kind);
 int dist_download(mgx_ctx *c, double *u, hipMemcpyKind kind);
 int dist_owned_rows(mgx_ctx *c, int part, int *ra, int *rb);
 int dist_download_rows(mgx_ctx *c, int part, double *out, hipMemcpyKind kind);
+// field diagnostics of a partitioned context (level 0; `who` names the C entry
+// point in messages): the owned rows of one local part, minus_rows holding
+// rows from minus_row0 on (the part's first owned row when < 0) ...
+int dist_field_stats_rows(mgx_ctx *c, int part, int field, int interior, const double *minus,
+                          long minus_row0, mgx_stats *out, const char *who);
+// ... and the whole grid of a local-parts context: the parts' records merged
+// in part order
+int dist_field_stats(mgx_ctx *c, int level, int field, int interior, const double *minus,
+                     mgx_stats *out);
+int dist_sample(mgx_ctx *c, int level, int field, long stride, double *out, bool device_out,
+                const char *who);
+int dist_sample_rows(mgx_ctx *c, int part, int field, long stride, double *out, long *first_row,
+                     long *rows);
 int dist_rhs(mgx_ctx *c);
 int dist_rhs_norm(mgx_ctx *c, double *res0);
 // whole-grid source (reference layout): every part keeps its owned rows, the

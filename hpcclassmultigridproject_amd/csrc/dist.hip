@@ -1404,6 +1404,148 @@ int dist_download_rows(mgx_ctx *c, int part, double *out, hipMemcpyKind kind) {
     return MGX_OK;
 }
 
+// ---------------------------------------------------------------- field diagnostics
+// Level-0 field `field` (0..3 as mgx_download_level, 4 = the source rows) of
+// local part `part` as a view, and the part's owned rows.  With every level
+// replicated it is the part's full copy in its sub-context.  Host checks
+// first; the only device call is the sub-context's materialize.
+static int part_view(mgx_ctx *c, int part, int field, const char *who, mgxdiag::View *v, int *ra,
+                     int *rb) {
+    Dist *d = c->dist;
+    if (part < 0 || part >= (int)d->parts.size())
+        return fail(MGX_E_ARG, std::string(who) + ": bad part");
+    if (field < 0 || field > 4)
+        return fail(MGX_E_ARG, std::string(who) + ": field must be 0..4 (u, rhs, v1, v2, source)");
+    plan_rows(c->N, 0, d->world, d->parts[part].rank, ra, rb);
+    if (d->la == 0) {
+        mgx_ctx *s = d->parts[part].sub;
+        if (field == 4 && !s->src) return fail(MGX_E_ARG, std::string(who) + ": no source is set");
+        return field_view(s, 0, field, v);
+    }
+    PLevel &L = d->parts[part].lv[0];
+    if (field == 4 && !L.src) return fail(MGX_E_ARG, std::string(who) + ": no source is set");
+    v->a = field == 0 ? L.u[L.cur] : field == 1 ? L.rhs : field == 2 ? L.v1 : field == 3 ? L.v2
+                                                                                         : L.src;
+    v->row0 = field == 4 ? L.ra : L.lo;   // the source copy holds the owned rows only
+    v->pitch = L.pitch;
+    v->n = L.n;
+    return MGX_OK;
+}
+
+int dist_field_stats_rows(mgx_ctx *c, int part, int field, int interior, const double *minus,
+                          long minus_row0, mgx_stats *out, const char *who) {
+    mgxdiag::View v;
+    int ra, rb;
+    HIPCHK(hipSetDevice(c->device));
+    CHK(settle(c));
+    CHK(part_view(c, part, field, who, &v, &ra, &rb));
+    return stats_view(c, v, ra, rb, interior, minus, minus_row0 < 0 ? ra : minus_row0, out);
+}
+
+int dist_field_stats(mgx_ctx *c, int level, int field, int interior, const double *minus,
+                     mgx_stats *out) {
+    Dist *d = c->dist;
+    const char *who = "mgx_field_stats";
+    if (!d->local)
+        return fail(MGX_E_ARG, "mgx_field_stats: an RCCL rank holds its own rows and this call "
+                               "does not communicate: call mgx_field_stats_rows on every rank "
+                               "and combine the records with mgx_stats_merge");
+    if (level != 0)
+        return fail(MGX_E_ARG, "mgx_field_stats: only level 0 is available on a partitioned "
+                               "context");
+    if (field < 0 || field > 4)
+        return fail(MGX_E_ARG, "mgx_field_stats: field must be 0..4 (u, rhs, v1, v2, source)");
+    if (field == 4 && !c->src_active) return fail(MGX_E_ARG, "mgx_field_stats: no source is set");
+    HIPCHK(hipSetDevice(c->device));
+    CHK(settle(c));
+    mgxdiag::timer_reset();
+    for (int p = 0; p < (int)d->parts.size(); ++p) {
+        mgx_stats s;
+        if (d->la == 0) {
+            // every level replicated: sub-context 0 holds the grid; the same row
+            // cut, so that the record is the merge of the parts' either way
+            mgxdiag::View v;
+            int ra, rb, r0, r1;
+            CHK(part_view(c, 0, field, who, &v, &r0, &r1));
+            plan_rows(c->N, 0, d->world, d->parts[p].rank, &ra, &rb);
+            CHK(stats_view(c, v, ra, rb, interior, minus, 0, &s));
+        } else {
+            CHK(dist_field_stats_rows(c, p, field, interior, minus, 0, &s, who));
+        }
+        if (p == 0)
+            *out = s;
+        else
+            mgxdiag::merge(out, s);
+    }
+    return MGX_OK;
+}
+
+static int check_stride(long n, long stride, const char *who) {
+    if (stride < 1 || stride > n || n % stride)
+        return fail(MGX_E_ARG, std::string(who) + ": stride must divide the level's n (1 <= "
+                                                  "stride <= n)");
+    return MGX_OK;
+}
+// the sampled rows A (fine rows A * stride) inside [ra, rb)
+static void sampled_rows(long ra, long rb, long stride, long *A0, long *A1) {
+    *A0 = (ra + stride - 1) / stride;
+    *A1 = (rb + stride - 1) / stride;
+}
+
+int dist_sample(mgx_ctx *c, int level, int field, long stride, double *out, bool device_out,
+                const char *who) {
+    Dist *d = c->dist;
+    if (!d->local)
+        return fail(MGX_E_ARG, std::string(who) + ": an RCCL rank holds its own rows and this "
+                                                  "call does not communicate: use mgx_sample_rows");
+    if (level != 0)
+        return fail(MGX_E_ARG, std::string(who) + ": only level 0 is available on a partitioned "
+                                                  "context");
+    if (field < 0 || field > 4)
+        return fail(MGX_E_ARG, std::string(who) + ": field must be 0..4 (u, rhs, v1, v2, source)");
+    if (field == 4 && !c->src_active) return fail(MGX_E_ARG, std::string(who) + ": no source is set");
+    CHK(check_stride(c->N, stride, who));
+    HIPCHK(hipSetDevice(c->device));
+    CHK(settle(c));
+    std::vector<SamplePiece> ps;
+    const int np = d->la == 0 ? 1 : (int)d->parts.size();
+    for (int p = 0; p < np; ++p) {
+        SamplePiece s;
+        int ra, rb;
+        CHK(part_view(c, p, field, who, &s.f, &ra, &rb));
+        if (d->la == 0) {
+            ra = 0;
+            rb = (int)c->N + 1;
+        }
+        sampled_rows(ra, rb, stride, &s.A0, &s.A1);
+        ps.push_back(s);
+    }
+    return sample_pieces(c, ps, stride, 0, c->N / stride + 1, out, device_out);
+}
+
+int dist_sample_rows(mgx_ctx *c, int part, int field, long stride, double *out, long *first_row,
+                     long *rows) {
+    const char *who = "mgx_sample_rows";
+    Dist *d = c->dist;
+    if (part < 0 || part >= (int)d->parts.size())
+        return fail(MGX_E_ARG, "mgx_sample_rows: bad part");
+    if (field < 0 || field > 4)
+        return fail(MGX_E_ARG, "mgx_sample_rows: field must be 0..4 (u, rhs, v1, v2, source)");
+    if (field == 4 && !c->src_active) return fail(MGX_E_ARG, "mgx_sample_rows: no source is set");
+    CHK(check_stride(c->N, stride, who));
+    SamplePiece s;
+    int ra, rb;
+    plan_rows(c->N, 0, d->world, d->parts[part].rank, &ra, &rb);
+    sampled_rows(ra, rb, stride, &s.A0, &s.A1);
+    *first_row = s.A0 * stride;
+    *rows = std::max<long>(0, s.A1 - s.A0);
+    if (!out || *rows == 0) return MGX_OK;
+    HIPCHK(hipSetDevice(c->device));
+    CHK(settle(c));
+    CHK(part_view(c, part, field, who, &s.f, &ra, &rb));
+    return sample_pieces(c, {s}, stride, s.A0, *rows, out, false);
+}
+
 // Row-block upload, correct tower: which partitioned coarse levels generate
 // their velocity (PLevel::vgen) from the block's level-0 factors.  Level l's
 // entry (i, j) is the finest (2^l i, 2^l j); the generator reads the row

@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "ctx.h"
+#include "diag.h"
 #include "sepvel.h"
 #include "source.h"
 #include "vfactor.h"
@@ -1122,6 +1123,7 @@ void free_ctx(mgx_ctx *c) {
     (void)hipFree(c->zrow);
     (void)hipFree(c->vga);
     (void)hipFree(c->src);
+    (void)hipFree(c->diag);
     if (c->hscal) (void)hipHostFree(c->hscal);
     for (auto &r : c->pending) {
         (void)hipEventDestroy(r.e0);
@@ -1552,6 +1554,192 @@ int mgx_download_rows(mgx_ctx *c, int part, double *rows) {
     if (c->dist) return dist_download_rows(c, part, rows, hipMemcpyDeviceToHost);
     if (part != 0) return fail(MGX_E_ARG, "mgx_download_rows: a single-GPU context has part 0 only");
     return download_impl(c, 0, 0, rows, hipMemcpyDeviceToHost);
+}
+
+}  // extern "C"
+
+// ---- field diagnostics (include/mgx.h "Field diagnostics", csrc/diag.hip)
+// The context's scratch (partial records + one result record), allocated by
+// the first statistics call: a context that never asks keeps no byte of it.
+static int diag_scratch(mgx_ctx *c, mgxdiag::Rec **p) {
+    if (!c->diag) HIPCHK(hipMalloc(&c->diag, mgxdiag::scratch_bytes(1)));
+    *p = static_cast<mgxdiag::Rec *>(c->diag);
+    return MGX_OK;
+}
+static void window(long n, long r0, long r1, int interior, long *ra, long *rb, long *j0,
+                   long *j1) {
+    *ra = interior ? std::max<long>(r0, 1) : r0;
+    *rb = interior ? std::min<long>(r1, n) : r1;
+    *j0 = interior ? 1 : 0;
+    *j1 = interior ? n - 1 : n;
+}
+int mgxi::stats_view(mgx_ctx *c, const mgxdiag::View &f, long r0, long r1, int interior,
+                     const double *minus, long minus_row0, mgx_stats *out) {
+    if (f.n + 1 > 512L * 4096) return fail(MGX_E_ARG, "mgx_field_stats: level too wide");
+    mgxdiag::Rec *scr = nullptr;
+    CHK(diag_scratch(c, &scr));
+    mgxdiag::StatsArgs A;
+    A.f = f;
+    A.minus = minus;
+    A.minus_row0 = minus_row0;
+    window(f.n, r0, r1, interior, &A.r0, &A.r1, &A.j0, &A.j1);
+    A.partials = scr;
+    A.out = scr + mgxdiag::kMaxPartials;
+    mgxdiag::PassTimer T;
+    T.begin(c->stream);
+    mgxdiag::launch_stats(A, c->stream);
+    T.end(c->stream);
+    CHK(check_launch("field statistics"));
+    mgxdiag::Rec h;
+    HIPCHK(hipMemcpyAsync(&h, A.out, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    mgxdiag::to_stats(h, f.n, A.r0, A.r1, A.j0, A.j1, out);
+    T.commit(8.0 * (double)out->count * (minus ? 2.0 : 1.0));
+    return MGX_OK;
+}
+int mgxi::sample_pieces(mgx_ctx *c, const std::vector<SamplePiece> &pieces, long stride, long A0,
+                        long rows, double *out, bool device_out) {
+    if (rows <= 0) return MGX_OK;
+    const long cols = pieces[0].f.n / stride + 1;
+    double *dst = out;
+    if (!device_out) HIPCHK(hipMalloc(&dst, sizeof(double) * (size_t)rows * (size_t)cols));
+    int rc = MGX_OK;
+    for (const SamplePiece &p : pieces) {
+        mgxdiag::launch_gather(p.f, stride, p.A0, p.A1, dst + (p.A0 - A0) * cols, cols, c->stream);
+        if ((rc = check_launch("field sample")) != MGX_OK) break;
+    }
+    if (rc == MGX_OK && !device_out &&
+        hipMemcpyAsync(out, dst, sizeof(double) * (size_t)rows * (size_t)cols,
+                       hipMemcpyDeviceToHost, c->stream) != hipSuccess)
+        rc = fail(MGX_E_HIP, "field sample: copy");
+    if (hipStreamSynchronize(c->stream) != hipSuccess && rc == MGX_OK)
+        rc = fail(MGX_E_HIP, "field sample: sync");
+    if (!device_out) (void)hipFree(dst);
+    return rc;
+}
+// host-only argument check of (level, field) on a single-GPU context
+static int field_check(mgx_ctx *c, int level, int field, const char *who) {
+    if (level < 0 || level >= c->L)
+        return fail(MGX_E_ARG, std::string(who) + ": level out of range");
+    if (field < 0 || field > 4)
+        return fail(MGX_E_ARG, std::string(who) + ": field must be 0..4 (u, rhs, v1, v2, source)");
+    if (field == 4 && (level != 0 || !c->src))
+        return fail(MGX_E_ARG, std::string(who) + ": no source is set (field 4 is the context's "
+                                                  "copy of it, level 0)");
+    return MGX_OK;
+}
+// what mgx_download_level(level, field) copies: the same materialize + U() route
+int mgxi::field_view(mgx_ctx *c, int level, int field, mgxdiag::View *v) {
+    HIPCHK(hipSetDevice(c->device));
+    CHK(materialize(c, level));
+    Level &L = c->lv[level];
+    v->a = field == 0 ? L.U() : field == 1 ? L.rhs : field == 2 ? L.v1 : field == 3 ? L.v2 : c->src;
+    v->row0 = 0;
+    v->pitch = L.pitch;
+    v->n = L.n;
+    return MGX_OK;
+}
+
+extern "C" {
+
+int mgx_stats_merge(mgx_stats *into, const mgx_stats *other) {
+    if (!into || !other) return fail(MGX_E_ARG, "mgx_stats_merge: null argument");
+    mgxdiag::merge(into, *other);
+    return MGX_OK;
+}
+int mgx_array_stats(const double *a, const double *minus, long n, int interior_only,
+                    mgx_stats *out) {
+    if (!a || !out || n < 1) return fail(MGX_E_ARG, "mgx_array_stats: bad args");
+    std::lock_guard<std::mutex> g(g_raw_mu);
+    int dev = 0;
+    HIPCHK(hipGetDevice(&dev));
+    static mgxdiag::Rec *scr = nullptr;
+    static int scr_dev = -1;
+    if (!scr || scr_dev != dev) {
+        HIPCHK(hipMalloc(&scr, mgxdiag::scratch_bytes(1)));
+        scr_dev = dev;
+    }
+    long r0, r1, j0, j1;
+    window(n, 0, n + 1, interior_only, &r0, &r1, &j0, &j1);
+    mgxdiag::timer_reset();
+    mgxdiag::PassTimer T;
+    T.begin(nullptr);
+    const bool ok = mgxdiag::launch_raw_stats(a, minus, n, r0, r1, j0, j1, scr,
+                                              scr + mgxdiag::kMaxPartials, nullptr);
+    T.end(nullptr);
+    if (!ok) return fail(MGX_E_ARG, "mgx_array_stats: n too large");
+    CHK(check_launch("mgx_array_stats"));
+    mgxdiag::Rec h;
+    HIPCHK(hipMemcpy(&h, scr + mgxdiag::kMaxPartials, sizeof(h), hipMemcpyDeviceToHost));
+    mgxdiag::to_stats(h, n, r0, r1, j0, j1, out);
+    T.commit(8.0 * (double)out->count * (minus ? 2.0 : 1.0));
+    return MGX_OK;
+}
+int mgx_field_stats(mgx_ctx *c, int level, int field, int interior_only, const double *minus,
+                    mgx_stats *out) {
+    if (!c || !out) return fail(MGX_E_ARG, "mgx_field_stats: null argument");
+    if (c->dist) return dist_field_stats(c, level, field, interior_only, minus, out);
+    CHK(field_check(c, level, field, "mgx_field_stats"));
+    mgxdiag::timer_reset();
+    mgxdiag::View v;
+    CHK(field_view(c, level, field, &v));
+    return stats_view(c, v, 0, v.n + 1, interior_only, minus, 0, out);
+}
+int mgx_field_stats_rows(mgx_ctx *c, int part, int field, int interior_only,
+                         const double *minus_rows, mgx_stats *out) {
+    if (!c || !out) return fail(MGX_E_ARG, "mgx_field_stats_rows: null argument");
+    if (c->dist) {
+        if (field == 4 && !c->src_active)
+            return fail(MGX_E_ARG, "mgx_field_stats_rows: no source is set");
+        mgxdiag::timer_reset();
+        return dist_field_stats_rows(c, part, field, interior_only, minus_rows, -1, out,
+                                     "mgx_field_stats_rows");
+    }
+    if (part != 0)
+        return fail(MGX_E_ARG, "mgx_field_stats_rows: a single-GPU context has part 0 only");
+    CHK(field_check(c, 0, field, "mgx_field_stats_rows"));
+    mgxdiag::timer_reset();
+    mgxdiag::View v;
+    CHK(field_view(c, 0, field, &v));
+    return stats_view(c, v, 0, v.n + 1, interior_only, minus_rows, 0, out);
+}
+static int stride_check(long n, long stride, const char *who) {
+    if (stride < 1 || stride > n || n % stride)
+        return fail(MGX_E_ARG, std::string(who) + ": stride must divide the level's n (1 <= "
+                                                  "stride <= n)");
+    return MGX_OK;
+}
+static int sample_impl(mgx_ctx *c, int level, int field, long stride, double *out,
+                       bool device_out, const char *who) {
+    if (stride < 1) return fail(MGX_E_ARG, std::string(who) + ": stride must be >= 1");
+    if (!c || !out) return fail(MGX_E_ARG, std::string(who) + ": null argument");
+    if (c->dist) return dist_sample(c, level, field, stride, out, device_out, who);
+    CHK(field_check(c, level, field, who));
+    CHK(stride_check(c->lv[level].n, stride, who));
+    SamplePiece p;
+    CHK(field_view(c, level, field, &p.f));
+    p.A0 = 0;
+    p.A1 = p.f.n / stride + 1;
+    return sample_pieces(c, {p}, stride, 0, p.A1, out, device_out);
+}
+int mgx_sample(mgx_ctx *c, int level, int field, long stride, double *out) {
+    return sample_impl(c, level, field, stride, out, false, "mgx_sample");
+}
+int mgx_sample_device(mgx_ctx *c, int level, int field, long stride, double *out) {
+    return sample_impl(c, level, field, stride, out, true, "mgx_sample_device");
+}
+int mgx_sample_rows(mgx_ctx *c, int part, int field, long stride, double *out, long *first_row,
+                    long *rows) {
+    if (stride < 1) return fail(MGX_E_ARG, "mgx_sample_rows: stride must be >= 1");
+    if (!c || !first_row || !rows) return fail(MGX_E_ARG, "mgx_sample_rows: null argument");
+    if (c->dist) return dist_sample_rows(c, part, field, stride, out, first_row, rows);
+    if (part != 0) return fail(MGX_E_ARG, "mgx_sample_rows: a single-GPU context has part 0 only");
+    CHK(field_check(c, 0, field, "mgx_sample_rows"));
+    CHK(stride_check(c->N, stride, "mgx_sample_rows"));
+    *first_row = 0;
+    *rows = c->N / stride + 1;
+    if (!out) return MGX_OK;
+    return sample_impl(c, 0, field, stride, out, false, "mgx_sample_rows");
 }
 
 static int no_dist(mgx_ctx *c, const char *what) {
@@ -2190,6 +2378,15 @@ extern "C" int mgx_get_tuning(const char *key, long *value) {
         double ms = 0;
         mgxvf::last_stats(&rounds, &ms);
         *value = key[8] == 'r' ? (long)rounds : (long)(ms * 1e3);
+        return MGX_OK;
+    }
+    // (read-only: the calling thread's last statistics call, mgx_field_stats*
+    // / mgx_array_stats -- device microseconds of its reduction launches and
+    // their compulsory bytes)
+    if (!strcmp(key, "stats_us") || !strcmp(key, "stats_bytes")) {
+        double us = 0, bytes = 0;
+        mgxdiag::last_pass(&us, &bytes);
+        *value = key[6] == 'u' ? (long)us : (long)bytes;
         return MGX_OK;
     }
     if (!strcmp(key, "vgen")) {

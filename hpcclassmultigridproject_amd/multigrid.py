@@ -11,6 +11,7 @@ All compute runs in libmgx.so on the GPU; this module only marshals arguments.
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import math
 
@@ -69,6 +70,11 @@ def write_uT(path, rows, N: int, r0: int = 0, r1: int = None, append=False, nthr
         raise ValueError("rows must hold (r1-r0)*(N+1) doubles")
     check(lib().mgx_write_uT(str(path).encode(), _np_ptr(rows), N, r0, r1, int(bool(append)),
                              nthreads))
+
+
+FieldStats = collections.namedtuple(
+    "FieldStats", "count nonfinite sum sum_abs sum_sq min max min_i min_j max_i max_j")
+FieldStats.__doc__ = "mgx_stats (include/mgx.h) as Multigrid.stats() returns it."
 
 
 class Multigrid:
@@ -234,6 +240,81 @@ class Multigrid:
         out = np.empty((n + 1) ** 2, dtype=np.float64)
         check(lib().mgx_download_level(self._h, level, f, _np_ptr(out)))
         return out
+
+    # -- field diagnostics on the device (mgx_field_stats, mgx_sample)
+    _FIELDS = {"u": 0, "rhs": 1, "v1": 2, "v2": 3, "source": 4}
+
+    def stats(self, field="u", level=0, interior=False, minus=None):
+        """One reduction pass over what download_level(level, field) would
+        return -> FieldStats (count, nonfinite, sum, sum_abs, sum_sq, min, max,
+        min_i, min_j, max_i, max_j; sums and extrema over the finite entries,
+        positions of the first occurrence in row-major order).  field: "u",
+        "rhs", "v1", "v2" or "source"; interior: rows and columns 1..n-1 only;
+        minus: a device tensor in the reference layout of that level -- the
+        statistics are then those of fl(field - minus).  A local-parts solver
+        takes level 0 (the parts' records merged in part order)."""
+        n = self.N if level == 0 else self.level_n(level)
+        s = _lib.Stats()
+        check(lib().mgx_field_stats(self._h, level, self._FIELDS[field], int(bool(interior)),
+                                    _lib.device_ptr(minus, (n + 1) ** 2, "minus"), C.byref(s)))
+        return FieldStats(*s.astuple())
+
+    def stats_rows(self, part=0, field="u", interior=False, minus=None):
+        """stats() of the owned finest-level rows [ra, rb) of local part `part`
+        (owned_rows), with global positions and no communication: what a rank
+        of a multi-process run calls, combining the ranks' records with
+        stats_merge.  minus: a device tensor of those rows, (rb-ra)*(N+1)."""
+        cnt = 0
+        if minus is not None:
+            ra, rb = self.owned_rows(part)
+            cnt = (rb - ra) * (self.N + 1)
+        s = _lib.Stats()
+        check(lib().mgx_field_stats_rows(self._h, part, self._FIELDS[field], int(bool(interior)),
+                                         _lib.device_ptr(minus, cnt, "minus"), C.byref(s)))
+        return FieldStats(*s.astuple())
+
+    def sample(self, stride, field="u", level=0, out=None):
+        """Every stride-th row and column of a field, gathered on the device:
+        bitwise download_level(level, field).reshape(n+1, n+1)[::stride,
+        ::stride] -> an (m+1, m+1) array, m = n/stride (stride must divide n).
+        out: a numpy array, or a device tensor the kernel writes directly."""
+        n = self.N if level == 0 else self.level_n(level)
+        if stride < 1 or n % stride:
+            raise _lib.MGXError(_lib.MGX_E_ARG, "sample: stride must divide the level's n")
+        m = n // stride
+        f = self._FIELDS[field]
+        if out is not None and not isinstance(out, np.ndarray):
+            check(lib().mgx_sample_device(self._h, level, f, stride,
+                                          _lib.device_ptr(out, (m + 1) ** 2, "out")))
+            return out
+        out = np.empty((m + 1, m + 1), dtype=np.float64) if out is None else out
+        if out.size != (m + 1) ** 2:
+            raise ValueError(f"out must hold {(m + 1) ** 2} doubles")
+        check(lib().mgx_sample(self._h, level, f, stride, _np_ptr(out)))
+        return out
+
+    def sample_rows(self, part, stride, field="u"):
+        """-> (first_row, array): the sampled rows i (i % stride == 0) among
+        the owned rows of local part `part`, rows x (N/stride+1); first_row is
+        the fine-grid index of the first of them."""
+        f = self._FIELDS[field]
+        first, rows = C.c_long(), C.c_long()
+        check(lib().mgx_sample_rows(self._h, part, f, stride, None, C.byref(first),
+                                    C.byref(rows)))
+        out = np.empty((rows.value, self.N // stride + 1), dtype=np.float64)
+        if rows.value:
+            check(lib().mgx_sample_rows(self._h, part, f, stride, _np_ptr(out), C.byref(first),
+                                        C.byref(rows)))
+        return first.value, out
+
+    def cfl(self):
+        """The CFL number max(max|v1|, max|v2|) * dt * N of the finest level's
+        velocity, from two stats() passes (multiplied in that order)."""
+        vmax = 0.0
+        for f in ("v1", "v2"):
+            s = self.stats(f)
+            vmax = max(vmax, abs(s.min), abs(s.max)) if s.count > s.nonfinite else vmax
+        return vmax * self.dt * self.N
 
     # -- ops (multigrid.cpp call sites)
     def rhs(self):

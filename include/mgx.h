@@ -305,7 +305,8 @@ int mgx_get_tuning(const char *key, long *value);
  * the kernel sources (csrc stencil.h, kernels.h, kernels.hip, wsmooth.hip,
  * xsmooth.hip, concatenated in that order -- the key the committed PMC
  * profiles are stamped with) and of every product source (those + ctx.h,
- * plan.h, sepvel.h, mgx.hip, dist.hip, include/mgx.h). */
+ * plan.h, sepvel.h, mgx.hip, dist.hip, vfactor.h, vfactor.hip, source.h,
+ * source.hip, diag.h, diag.hip, include/mgx.h). */
 const char *mgx_build_id(void);
 const char *mgx_build_sources_id(void);
 
@@ -491,6 +492,75 @@ int mgx_source_info(mgx_ctx *ctx, int *active, double *scale);
 int mgx_compute_rhs_source(double *rhs, const double *u, long n, const double *v1,
                            const double *v2, double k, double nu, double h, const double *f,
                            double c);
+
+/* ---- Field diagnostics: statistics and strided samples on the device --------
+ * A context keeps its fields in HBM; these calls look at one without moving
+ * it (csrc/diag.hip, part of mgx_build_sources_id): one reduction pass over
+ * the field gives the record below, a gather kernel a coarse picture.  No
+ * floating-point atomics: the order of every addition is a fixed function of
+ * the grid size and the row range, so two calls give the same bits.  Every
+ * call here checks its arguments before any device call and reports
+ * MGX_E_ARG with a message that starts with its own name.  None of them
+ * changes a pass of a context that never calls them, and like the downloads
+ * they leave a pending next step or a speculative pre-smoothed u alone.
+ * Measured on one MI355X: mgx_field_stats of u at
+ * N=16384 takes 0.38 ms of device time (0.74 ms with minus), mgx_sample at
+ * stride 64 0.05 ms, against 136 ms for mgx_download alone. */
+typedef struct mgx_stats {
+    long   count;        /* points examined */
+    long   nonfinite;    /* NaN or +-Inf among them */
+    double sum, sum_abs, sum_sq;   /* over the FINITE values: x, |x|, fl(x*x) */
+    double min, max;     /* over the finite values; +Inf / -Inf when there is none */
+    long   min_i, min_j, max_i, max_j;  /* global (row, column) of the first occurrence
+                                           in row-major order; -1 when there is none */
+} mgx_stats;
+/* min and max compare by value (-0 == +0); among equal values the first in
+ * row-major order wins and min / max carry that element's bits -- what
+ * np.argmin / np.argmax give on the finite entries.
+ *
+ * The gs.h-style raw op: device pointers in the reference layout ((n+1)^2
+ * row-major), any n >= 1, null stream; synchronises (like mgx_compute_norm).
+ * minus != NULL: the statistics of d = fl(a - minus), point by point.
+ * interior_only = 1: rows and columns 1..n-1 only (count (n-1)^2). */
+int mgx_array_stats(const double *a, const double *minus, long n, int interior_only,
+                    mgx_stats *out);
+/* The statistics of what mgx_download_level(level, field) would return, on the
+ * context's stream.  field 0..3 as there, 4 = the context's copy of the source
+ * (level 0; MGX_E_ARG when none is set).  minus: a device pointer in the
+ * reference layout of that level, or NULL.  A local-parts context
+ * (mgx_create_local_dist) takes level 0 only: the result is mgx_stats_merge of
+ * its parts' owned-row results in part order (of sub-context 0 when every
+ * level is replicated).  An RCCL rank returns MGX_E_ARG: it performs no
+ * communication -- call mgx_field_stats_rows and merge the ranks' records. */
+int mgx_field_stats(mgx_ctx *ctx, int level, int field, int interior_only, const double *minus,
+                    mgx_stats *out);
+/* The owned finest-level rows [ra, rb) (mgx_owned_rows) of local part `part`,
+ * with global positions; minus_rows holds those rows only, (rb-ra)*(N+1)
+ * doubles on the device, or NULL.  No communication; any context (a
+ * single-GPU context has part 0 = all rows).  What an RCCL rank calls. */
+int mgx_field_stats_rows(mgx_ctx *ctx, int part, int field, int interior_only,
+                         const double *minus_rows, mgx_stats *out);
+/* Host only (no HIP call): *into = the record of the union.  Counts and sums
+ * add; min / max by value, ties to the smaller (i, j) in row-major order; an
+ * operand without a finite value leaves the other's extrema unchanged. */
+int mgx_stats_merge(mgx_stats *into, const mgx_stats *other);
+/* out[a*(m+1)+b] = field(a*stride, b*stride), m = n/stride: bitwise the
+ * entries [::stride, ::stride] of mgx_download_level.  stride must divide the
+ * level's n (1 <= stride <= n).  mgx_sample: host `out` (a gather kernel into
+ * a compact device buffer, then one copy); mgx_sample_device: device `out`,
+ * written by the kernel.  Local-parts contexts: level 0, each part its owned
+ * rows; an RCCL rank returns MGX_E_ARG (use mgx_sample_rows). */
+int mgx_sample(mgx_ctx *ctx, int level, int field, long stride, double *out);
+int mgx_sample_device(mgx_ctx *ctx, int level, int field, long stride, double *out);
+/* The sampled rows i in [ra, rb) with i % stride == 0 of local part `part`
+ * into the host array out[*rows * (N/stride+1)]; *first_row = the global
+ * fine-grid index of the first of them.  out == NULL only reports first_row
+ * and rows.  Any context, no communication. */
+int mgx_sample_rows(mgx_ctx *ctx, int part, int field, long stride, double *out,
+                    long *first_row, long *rows);
+/* (Read-only, mgx_get_tuning, beside "vfactor_us": "stats_us" / "stats_bytes"
+ * = the device microseconds -- HIP events around the reduction launches only
+ * -- and the compulsory bytes of the calling thread's last statistics call.) */
 
 #ifdef __cplusplus
 }
