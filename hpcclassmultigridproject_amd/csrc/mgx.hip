@@ -1900,9 +1900,10 @@ int mgx_profile_enable(mgx_ctx *c, int on) {
     CHK(prof_flush(c));
     if (on < 0 || on > 2) return fail(MGX_E_ARG, "mgx_profile_enable: on must be 0, 1 or 2");
     c->prof = on;
-    // the replicated levels of a partitioned context are never the finest
-    for (int i = 0; i < dist_nsub(c); ++i)
-        CHK(mgx_profile_enable(dist_sub(c, i), on == 1 ? 1 : 0));
+    // the replicated levels of a partitioned context are not the finest,
+    // unless everything is replicated (first replicated level 0)
+    const int sub_on = on == 1 ? 1 : (on == 2 && dist_la(c) == 0 ? 2 : 0);
+    for (int i = 0; i < dist_nsub(c); ++i) CHK(mgx_profile_enable(dist_sub(c, i), sub_on));
     return MGX_OK;
 }
 int mgx_profile_reset(mgx_ctx *c) {

@@ -322,7 +322,10 @@ const char *mgx_build_sources_id(void);
 #define MGX_K_XSMOOTH 8        /* finest level: post-smoothing of cycle k + pre-smoothing of k+1 */
 #define MGX_K_COUNT 9
 /* on: 0 off, 1 every launch, 2 finest-level launches only (two events per
- * recorded launch; mode 2 keeps the overhead off the small levels). */
+ * recorded launch; mode 2 keeps the overhead off the small levels).
+ * Partitioned contexts: the replicated levels are recorded in mode 1, and in
+ * mode 2 only where everything is replicated (the first replicated level is
+ * 0, mgx_dist_info), the finest level then being one of them. */
 int mgx_profile_enable(mgx_ctx *ctx, int on);
 int mgx_profile_reset(mgx_ctx *ctx);
 /* For kernel kind `kind` on level `level` (-1 = all levels): launches, summed

@@ -1,0 +1,245 @@
+"""Seeded test fields that share nothing with init_problem (numpy only).
+
+init_problem(N) is a Gaussian that is ~1e-40 over most of the grid with an
+exactly zero boundary, carried by the rotating flow -- an exact rank-1 product
+of sin/cos factors.  The fields here have none of those properties, so a test
+that feeds them to the solver and to the CPU checker exercises the general
+code: the 2-D velocity reads, non-zero Dirichlet data in u, coarse velocity
+rows that are not zero, and factors the separable-velocity kernels have never
+seen.
+
+All arrays are flat float64 in the reference layout ((N+1)^2, row-major, i
+outer).  Everything is a pure function of (N, seed): the solver and the
+checker receive the same arrays at run time, so no bits are pinned across
+machines or numpy versions.
+"""
+import numpy as np
+
+NU = -4e-4
+# name -> (dt(N), nu).  "easy" is the reference main's time step; "stiff" is
+# ten times that: convection and diffusion numbers dt|v|/h <= 3.5, dt|nu|/h^2 =
+# 4e-4 N, at which a V-cycle takes 5-6 cycles to 1e-9 on generic() and the
+# multi-cycle state (speculative pre-smoothing, predicted stores, step fusion)
+# is exercised.  dt = 3/N with nu = -2e-3 diverges in the checker: stay at or
+# below the stiff numbers.
+PARAMS = {
+    "easy": (lambda N: 1.0 / (10 * N), NU),
+    "stiff": (lambda N: 1.0 / N, NU),
+}
+
+
+# Every (field, params, nsmooth, shape, tol) a GPU test runs through mg_outer or
+# step (tests/test_gpu_generic_fields.py); tests/test_fields.py checks on the
+# checker alone that no per-cycle norm of these sits within MARGIN of tol.
+# field: "generic" (boundary=True), "generic0" (boundary=False), "rank1" (u0 of
+# generic, the velocity of rank1_flow).
+TOL = 1e-9
+CONVERGENCE_CASES = [
+    ("generic", "stiff", 3, 1, TOL),
+    ("generic", "stiff", 2, 1, TOL),
+    ("generic", "stiff", 3, 2, TOL),
+    ("generic0", "stiff", 3, 1, TOL),
+    ("generic", "easy", 3, 1, TOL),
+    ("rank1", "stiff", 3, 1, TOL),
+]
+SEED = 1
+
+
+def make(field, N, seed=SEED):
+    """-> (u0, v1, v2) of a CONVERGENCE_CASES field name."""
+    u0, v1, v2 = generic(N, seed, boundary=field != "generic0")
+    if field == "rank1":
+        v1, v2 = rank1_flow(N, seed)
+    return u0, v1, v2
+
+
+def params(name, N):
+    """-> (dt, nu) of PARAMS[name] at size N."""
+    dt, nu = PARAMS[name]
+    return dt(N), nu
+
+
+def _grid(N):
+    x = np.arange(N + 1) / N
+    return np.meshgrid(x, x, indexing="ij")
+
+
+def generic(N, seed, boundary=True):
+    """-> (u0, v1, v2): O(1) everywhere, smooth modes plus per-point noise.
+
+    u0: a bump, a non-separable mode and N(0, .05) noise; with boundary=True
+    its ring (rows and columns 0 and N) is non-zero and non-constant, with
+    boundary=False it is exactly zero.
+    v1, v2: non-separable, |v| <= 3.3 and 2.8, per-point noise, sign changes,
+    no symmetry between the two, non-zero on the boundary rows and columns.
+    The rng draws are in the order u, v1, v2."""
+    rng = np.random.default_rng(seed)
+    X, Y = _grid(N)
+    u = (np.exp(-30 * ((X - .6) ** 2 + (Y - .3) ** 2)) + .5 * np.sin(3 * np.pi * X * Y + 1)
+         + .05 * rng.standard_normal(X.shape))
+    v1 = 2 * np.cos(2 * np.pi * X * Y) + np.sin(5 * Y) + .3 * rng.uniform(-1, 1, X.shape)
+    v2 = -1.5 * np.sin(3 * X + Y ** 2) + np.cos(4 * np.pi * X) * Y + .3 * rng.uniform(-1, 1, X.shape)
+    if not boundary:
+        u[0, :] = u[N, :] = 0.0
+        u[:, 0] = u[:, N] = 0.0
+    return tuple(np.ascontiguousarray(a).ravel() for a in (u, v1, v2))
+
+
+def _factor(rng, N, phase, unit=None):
+    """One factor of rank1_flow: smooth + noise, sign changes, magnitudes in
+    [1e-3, 1.8] (so |a_i b_j| <= 3.24, the convection number of generic()),
+    three exact zeros (one of them -0.0), optionally one exact 1."""
+    x = np.arange(N + 1) / N
+    f = 1.2 * np.sin(2.3 * np.pi * x + phase) + .4 * (x - .4) + .25 * rng.uniform(-1, 1, N + 1)
+    small = np.abs(f) < 1e-3
+    f[small] = np.where(f[small] < 0, -1e-3, 1e-3)
+    # one entry at each end of the range
+    f[(N * 5) // 7] = 1.8
+    f[(N * 2) // 7] = -1e-3
+    z = [N // 9 + 1, N // 2 + 3, N - 5]
+    f[z[0]] = 0.0
+    f[z[1]] = -0.0
+    f[z[2]] = 0.0
+    if unit is not None:
+        f[unit] = 1.0
+    return f
+
+
+def rank1_unit_columns(N):
+    """The columns j* with b[j*] = 1.0 exactly of rank1_flow's v1 and v2: two
+    of the columns csrc/sepvel.h tries, neither of them the rotating flow's
+    (0 for v1, (N+1)/2 for v2)."""
+    w = N + 1
+    return w // 4, (3 * w) // 4
+
+
+def rank1_factors(N, seed):
+    """-> (a1, b1, a2, b2) of rank1_flow (the rng draws in this order)."""
+    rng = np.random.default_rng(seed)
+    j1, j2 = rank1_unit_columns(N)
+    a1 = _factor(rng, N, 0.3)
+    b1 = _factor(rng, N, 1.1, unit=j1)
+    a2 = _factor(rng, N, 2.0)
+    b2 = _factor(rng, N, -0.7, unit=j2)
+    return a1, b1, a2, b2
+
+
+def rank1_flow(N, seed):
+    """-> (v1, v2) with v[i][j] = fl(a_i * b_j) (np.multiply.outer): an exact
+    rank-1 product whose factors are not sin/cos -- smooth plus noise, sign
+    changes, a few exactly zero a rows and b columns (one -0.0 in each),
+    magnitudes within 1e-3..1.8, and b[j*] = 1.0 exactly at rank1_unit_columns.
+
+    The property mgx_factor_velocity needs: it reads the row factors off a
+    column whose b is exactly 1.0, looking only at columns 0, w/4, w/2, 3w/4
+    and w-1 (w = N+1); without a unit entry at one of those it refuses the
+    field, however exact the product."""
+    a1, b1, a2, b2 = rank1_factors(N, seed)
+    return (np.multiply.outer(a1, b1).ravel(), np.multiply.outer(a2, b2).ravel())
+
+
+def factor(v, N, smin=0.0):
+    """mgx_factor_velocity (host only) on rows x (N+1) entries -> (ok, a, b)."""
+    from hpcclassmultigridproject_amd import _lib
+    rows = v.size // (N + 1)
+    a, b = np.empty(rows), np.empty(N + 1)
+    r = _lib.lib().mgx_factor_velocity(v.ctypes.data, rows, N, smin, a.ctypes.data, b.ctypes.data)
+    assert r in (0, 1), _lib.lib().mgx_last_error()
+    return bool(r), a, b
+
+
+# ---- the CPU checker driven cycle by cycle (oracle.oracle passed in as O)
+#
+# or_mg_outer / or_timestepper return the cycle counts and the first and last
+# norm only.  The tests also need every norm in between -- a cycle count is
+# only comparable where no r_k / r_0 sits within rounding of tol -- so these
+# mirror the two loops (oracle/mg_oracle.c, multigrid.cpp:97-120 and :165-172)
+# around the checker's own mg_inner, residual and norm.  tests/test_fields.py
+# pins them bit for bit to the C loops.
+
+MARGIN = 0.01   # every r_k / r_0 at least 1 % away from tol
+
+
+def accurate_norm(res, n):
+    """compute_norm (gs.cpp:86) of a residual with the squares summed pairwise
+    in the widest float numpy has: relative error <= log2(M) eps ~ 3e-15 even
+    where that is float64 (M = 6.7e7 points at n = 8192), against M eps / 2 =
+    3.7e-9 for the reference's serial loop.  tests/test_fields.py pins it to
+    math.fsum."""
+    r = res.reshape(n + 1, n + 1)[1:n, 1:n]
+    return float(np.sqrt(np.sum(r * r, dtype=np.longdouble)))
+
+
+class Norm(float):
+    """A norm as the checker's serial loop returns it -- the value the
+    checker's own loops decide on -- with .exact, the accurately summed norm
+    of the same residual.
+
+    The serial sum is not a reference for the value: measured on generic()
+    (seed 1) against math.fsum of the checker's squared residual, it is off by
+    1.4e-11 and 1.5e-10 relative after the two easy steps at N=8192 and by
+    3.0e-11 after the W-cycles at N=4096, where the solver's tree sum is
+    within 1.8e-16 of fsum.  So a GPU norm is compared with .exact (to the
+    1e-11 include/mgx.h documents), and the serial value must itself lie
+    within its own error bound of it (tests/test_fields.py)."""
+
+    def __new__(cls, serial, exact):
+        x = super().__new__(cls, serial)
+        x.exact = exact
+        return x
+
+
+class CheckerRun:
+    """A checker tower plus the norms of everything run on it."""
+
+    def __init__(self, O, u0, v1, v2, N, L, dt, nu, tower=0, nsmooth=3, shape=1, fp=0):
+        self.O, self.N, self.L, self.dt, self.nu = O, N, L, dt, nu
+        self.nsmooth, self.shape, self.fp = nsmooth, shape, fp
+        self.t = O.Tower(u0, v1, v2, N, L, tower)
+        self.v1, self.v2 = self.t._keep[1], self.t._keep[2]
+
+    @property
+    def u(self):
+        return self.t.ufine
+
+    def rhs(self):
+        self.O.compute_rhs(self.u, self.N, self.v1, self.v2, self.dt, self.nu, 1.0 / self.N,
+                           rhs=self.t.rhsfine)
+
+    def norm(self, reference_form=False):
+        """The residual norm of the finest level; reference_form: in the
+        reference's term order whatever the fp mode (mg_outer's first norm)."""
+        O = self.O
+        if reference_form:
+            O.set_fp_mode(0)
+        O.residual(self.u, self.t.rhsfine, self.N, self.v1, self.v2, self.dt, self.nu,
+                   1.0 / self.N, res=self.t.tmp)
+        if reference_form:
+            O.set_fp_mode(self.fp)
+        return Norm(O.compute_norm(self.t.tmp, self.N), accurate_norm(self.t.tmp, self.N))
+
+    def cycle(self):
+        """One V / W cycle -> the residual norm after it."""
+        self.t.mg_inner(self.dt, self.nu, shape=self.shape, nsmooth=self.nsmooth)
+        return self.norm()
+
+    def mg_outer(self, tol, max_cycle=50):
+        """-> (cycles, r0, [r_1 .. r_cycles])"""
+        r0 = self.norm(reference_form=True)
+        res, norms = r0, []
+        while len(norms) < max_cycle and res / r0 > tol:
+            res = self.cycle()
+            norms.append(res)
+        return len(norms), r0, norms
+
+    def step(self, tol):
+        self.rhs()
+        return self.mg_outer(tol)
+
+    def close(self):
+        self.t.close()
+
+
+def margin(r0, norms, tol):
+    """The smallest |r_k / (tol r_0) - 1| over the cycles of one mg_outer."""
+    return min(abs(r / (tol * r0) - 1.0) for r in norms) if norms else 1.0
