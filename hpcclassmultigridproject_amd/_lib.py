@@ -18,6 +18,8 @@ MGX_OK, MGX_E_ARG, MGX_E_HIP, MGX_E_RCCL, MGX_E_NOCONV = 0, 1, 2, 3, 4
 TOWER_REFERENCE, TOWER_CORRECT = 0, 1
 FP_BITWISE, FP_FMA = 0, 1   # mgx_options.fp_mode
 UNIQUE_ID_BYTES = 128   # MGX_UNIQUE_ID_BYTES (ncclUniqueId)
+MGX_SOURCE_MAX_TERMS = 4   # terms of a separable source (mgx_set_source_separable)
+SOURCE_NONE, SOURCE_FIELD, SOURCE_SEPARABLE = 0, 1, 2   # mgx_source_kind
 K_GS, K_RESTRICT, K_PROLONG, K_RESNORM, K_COARSE, K_RHS, K_HALO, K_PSMOOTH, K_XSMOOTH = range(9)
 KERNEL_NAMES = {K_GS: "gs_sweep", K_RESTRICT: "residual_restrict", K_PROLONG: "prolong_add",
                 K_RESNORM: "residual_norm", K_COARSE: "coarse_solve", K_RHS: "compute_rhs",
@@ -123,6 +125,13 @@ _SIGS = {
     "mgx_set_source_scale": (_I, [_vp, _D]),
     "mgx_source_info": (_I, [_vp, C.POINTER(_I), _dp]),
     "mgx_compute_rhs_source": (_I, [_vp, _vp, _L, _vp, _vp, _D, _D, _D, _vp, _D]),
+    "mgx_set_source_separable": (_I, [_vp, _I, _vp, _vp]),
+    "mgx_set_source_separable_device": (_I, [_vp, _I, _vp, _vp]),
+    "mgx_set_source_rows": (_I, [_vp, C.POINTER(_vp)]),
+    "mgx_set_source_rows_device": (_I, [_vp, C.POINTER(_vp)]),
+    "mgx_source_kind": (_I, [_vp, C.POINTER(_I), C.POINTER(_I)]),
+    "mgx_compute_rhs_source_separable": (_I, [_vp, _vp, _L, _vp, _vp, _D, _D, _D, _I, _vp, _vp,
+                                              _D]),
     "mgx_array_stats": (_I, [_vp, _vp, _L, _I, C.POINTER(Stats)]),
     "mgx_field_stats": (_I, [_vp, _I, _I, _I, _vp, C.POINTER(Stats)]),
     "mgx_field_stats_rows": (_I, [_vp, _I, _I, _I, _vp, C.POINTER(Stats)]),
@@ -208,6 +217,22 @@ def compute_rhs_source(rhs, u, n, v1, v2, k, nu, h, f, c):
         return x.data_ptr()
     check(lib().mgx_compute_rhs_source(ptr(rhs), ptr(u), n, ptr(v1), ptr(v2), k, nu, h, ptr(f),
                                        c))
+
+
+def compute_rhs_source_separable(rhs, u, n, v1, v2, k, nu, h, a, b, c):
+    """mgx_compute_rhs_source_separable: compute_rhs_source with the source
+    given by its factors, f = a[0] x b[0] (+ a[1] x b[1] ...) summed left to
+    right.  a, b: device tensors of (terms, n+1) float64 (or n+1 for one
+    term); the rest as compute_rhs_source."""
+    terms = 1 if a.dim() == 1 else a.shape[0]
+    if not 1 <= terms <= MGX_SOURCE_MAX_TERMS:
+        raise ValueError(f"1..{MGX_SOURCE_MAX_TERMS} terms")
+    for x in (a, b):
+        if x.numel() != terms * (n + 1) or not x.is_contiguous() or x.element_size() != 8:
+            raise ValueError("a, b: contiguous float64 tensors of (terms, n+1) entries")
+    ptrs = [device_ptr(x, (n + 1) * (n + 1)) for x in (rhs, u, v1, v2)]
+    check(lib().mgx_compute_rhs_source_separable(ptrs[0], ptrs[1], n, ptrs[2], ptrs[3], k, nu, h,
+                                                 terms, a.data_ptr(), b.data_ptr(), c))
 
 
 def device_ptr(x, count, what="tensor"):

@@ -96,6 +96,15 @@ struct mgx_ctx {
     double *src = nullptr;
     double src_scale = 1.0;
     bool src_active = false;
+    // mgx_set_source_separable: src_terms > 0 = the source is the sum of that
+    // many outer products (source.h) and no copy of f exists.  src_a: the row
+    // factors, MGX_SOURCE_MAX_TERMS x (N+1); src_b: the column factors,
+    // MGX_SOURCE_MAX_TERMS x finest pitch, zero padded -- allocated by the first
+    // call, reused by every replacement.  A partitioned context keeps the
+    // factors in its parts (dist.hip) and src_terms here.
+    int src_terms = 0;
+    double *src_a = nullptr, *src_b = nullptr;
+    bool has_source() const { return src != nullptr || src_terms > 0; }
     // scratch of the field diagnostics (diag.h: partial records + the result),
     // allocated by the first statistics call
     void *diag = nullptr;
@@ -204,6 +213,15 @@ int upload_ctx(mgx_ctx *c, const double *u0, const double *v1, const double *v2,
 // state formed from the old right-hand side is dropped
 int set_source_ctx(mgx_ctx *c, const double *f, hipMemcpyKind kind);
 void drop_source_state(mgx_ctx *c);
+// mgx_set_source_separable on a single-GPU context: a, b hold terms x (N+1)
+// doubles, term-major (checked by the caller); replaces a field source
+int set_source_sep_ctx(mgx_ctx *c, int terms, const double *a, const double *b,
+                       hipMemcpyKind kind);
+// the device copies of separable factors (ctx.h mgx_ctx::src_a / src_b layout
+// for a level of n+1 columns and the given pitch), allocated where *da / *db
+// are null; who: the C entry point, for the message
+int copy_source_factors(double **da, double **db, long n, long pitch, int terms, const double *a,
+                        const double *b, hipMemcpyKind kind, hipStream_t s, const char *who);
 // tuning key "source_sv" (mgx.hip): the source pass reads the finest level's
 // velocity factors, where the context keeps them, instead of the 2-D v1 / v2
 extern long g_source_sv;
@@ -252,6 +270,13 @@ int dist_rhs_norm(mgx_ctx *c, double *res0);
 // whole-grid source (reference layout): every part keeps its owned rows, the
 // replicated sub-contexts of a fully replicated context the whole field
 int dist_set_source(mgx_ctx *c, const double *f, hipMemcpyKind kind);
+// mgx_set_source_rows: f[i] = the owned rows of local part i (null entries
+// refused by the caller)
+int dist_set_source_rows(mgx_ctx *c, const double *const *f, hipMemcpyKind kind);
+// mgx_set_source_separable: every part (or replicated sub-context) keeps the
+// factors
+int dist_set_source_sep(mgx_ctx *c, int terms, const double *a, const double *b,
+                        hipMemcpyKind kind);
 void dist_set_source_scale(mgx_ctx *c, double s);
 int dist_vcycle(mgx_ctx *c, double *norm, bool store_post = true);
 // partitioned level 0 runs the cross-cycle pass; recompute its unstored u_post

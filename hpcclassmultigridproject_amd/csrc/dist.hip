@@ -112,6 +112,12 @@ struct PLevel {
     // level 0: this part's owned rows [ra, rb) of the source (mgx_set_source),
     // pitched, or null
     double *src = nullptr;
+    // level 0: the factors of a separable source (mgx_set_source_separable;
+    // mgx_ctx::src_a / src_b layout, the row factors full length and indexed by
+    // the GLOBAL row), src_terms > 0 while one is set
+    double *src_a = nullptr, *src_b = nullptr;
+    int src_terms = 0;
+    bool has_source() const { return src != nullptr || src_terms > 0; }
     // level 0: exact velocity factors (sepvel.h) indexed by GLOBAL row / column
     // (full-length arrays, this block's rows filled), or null
     double *sa1 = nullptr, *sb1 = nullptr, *sa2 = nullptr, *sb2 = nullptr;
@@ -195,6 +201,8 @@ void dist_free(mgx_ctx *c) {
             (void)hipFree(L.v1);
             (void)hipFree(L.v2);
             (void)hipFree(L.src);
+            (void)hipFree(L.src_a);
+            (void)hipFree(L.src_b);
             for (double *f : {L.sa1, L.sb1, L.sa2, L.sb2}) (void)hipFree(f);
         }
         if (p.sub) free_ctx(p.sub);
@@ -1017,7 +1025,11 @@ static mgxsrc::SrcArgs source_args(mgx_ctx *c, Part &p, bool norm, double *cbyte
     A.u = L.U();
     A.v1 = L.F(L.v1);
     A.v2 = L.F(L.v2);
-    A.f = L.src - (long)L.ra * L.pitch;   // + r*pitch = global row r, r in [ra, rb)
+    // + r*pitch = global row r, r in [ra, rb)
+    A.f = L.src ? L.src - (long)L.ra * L.pitch : nullptr;
+    A.terms = L.src_terms;   // > 0: the separable form, no f stream
+    A.fa = L.src_a;
+    A.fb = L.src_b;
     A.cf = c->dt * c->src_scale;
     A.n = L.n;
     A.pitch = L.pitch;
@@ -1036,7 +1048,7 @@ static mgxsrc::SrcArgs source_args(mgx_ctx *c, Part &p, bool norm, double *cbyte
         A.norm_out = p.dsum;
         A.take_sqrt = false;
     }
-    *cbytes = (sv ? 24.0 : 40.0) * L.Mown();
+    *cbytes = ((sv ? 16.0 : 32.0) + (A.terms ? 0.0 : 8.0)) * L.Mown();
     return A;
 }
 
@@ -1052,10 +1064,10 @@ int dist_rhs(mgx_ctx *c) {
     CHK(xchg(c, 0, kU));
     for (auto &p : d->parts) {
         PLevel &L = p.lv[0];
-        if (L.src) {
+        if (L.has_source()) {
             double cb = 0;
             const mgxsrc::SrcArgs A = source_args(c, p, false, &cb);
-            CHK(launch(c, MGX_K_RHS, 0, 40.0 * L.Mown(), cb,
+            CHK(launch(c, MGX_K_RHS, 0, (A.terms ? 32.0 : 40.0) * L.Mown(), cb,
                        [&] { mgxsrc::launch_rhs_source(A, c->stream); }));
             continue;
         }
@@ -1081,10 +1093,10 @@ int dist_rhs_norm(mgx_ctx *c, double *res0) {
     CHK(xchg(c, 0, kU));
     for (auto &p : d->parts) {
         PLevel &L = p.lv[0];
-        if (L.src) {
+        if (L.has_source()) {
             double cb = 0;
             const mgxsrc::SrcArgs A = source_args(c, p, true, &cb);
-            CHK(launch(c, MGX_K_RHS, 0, 88.0 * L.Mown(), cb,
+            CHK(launch(c, MGX_K_RHS, 0, (A.terms ? 80.0 : 88.0) * L.Mown(), cb,
                        [&] { mgxsrc::launch_rhs_source(A, c->stream); }));
             continue;
         }
@@ -1111,24 +1123,28 @@ static void free_sources(mgx_ctx *c) {
     }
     c->src_active = false;
 }
-int dist_set_source(mgx_ctx *c, const double *f, hipMemcpyKind kind) {
-    Dist *d = c->dist;
-    HIPCHK(hipSetDevice(c->device));
-    CHK(settle(c));
-    dist_set_source_scale(c, c->src_scale);   // drops the speculative states
-    if (d->la == 0) {
-        int rc = MGX_OK;
-        for (auto &p : d->parts)
-            if (rc == MGX_OK) rc = set_source_ctx(p.sub, f, kind);
-        if (rc != MGX_OK)   // all parts or none
-            for (auto &p : d->parts) (void)set_source_ctx(p.sub, nullptr, kind);
-        c->src_active = rc == MGX_OK && f;
-        return rc;
+// the separable source of every part goes (one source per context)
+static void free_source_factors(mgx_ctx *c) {
+    for (auto &p : c->dist->parts) {
+        if (!p.lv.empty()) {
+            PLevel &L = p.lv[0];
+            (void)hipFree(L.src_a);
+            (void)hipFree(L.src_b);
+            L.src_a = L.src_b = nullptr;
+            L.src_terms = 0;
+        }
     }
-    if (!f) {
-        HIPCHK(hipStreamSynchronize(c->stream));   // a pass may still read the copies
-        free_sources(c);
-        return MGX_OK;
+    if (c->src_terms) c->src_active = false;
+    c->src_terms = 0;
+}
+// every part's owned rows from block(part) (reference layout, host or device)
+// into PLevel::src: all parts or none
+template <class B>
+static int set_source_blocks(mgx_ctx *c, B block, hipMemcpyKind kind) {
+    Dist *d = c->dist;
+    if (c->src_terms) {
+        HIPCHK(hipStreamSynchronize(c->stream));   // a pass may still read the factors
+        free_source_factors(c);
     }
     const size_t row = (c->N + 1) * sizeof(double);
     auto copy_all = [&]() -> int {
@@ -1146,9 +1162,8 @@ int dist_set_source(mgx_ctx *c, const double *f, hipMemcpyKind kind) {
                 }
                 HIPCHK(hipMemsetAsync(L.src, 0, bytes, c->stream));
             }
-            HIPCHK(hipMemcpy2DAsync(L.src, L.pitch * sizeof(double),
-                                    f + (long)L.ra * (c->N + 1), row, row, L.rb - L.ra, kind,
-                                    c->stream));
+            HIPCHK(hipMemcpy2DAsync(L.src, L.pitch * sizeof(double), block(p), row, row,
+                                    L.rb - L.ra, kind, c->stream));
         }
         HIPCHK(hipStreamSynchronize(c->stream));   // the caller's buffer is free on return
         return MGX_OK;
@@ -1159,6 +1174,78 @@ int dist_set_source(mgx_ctx *c, const double *f, hipMemcpyKind kind) {
         free_sources(c);
         return rc;
     }
+    c->src_active = true;
+    return MGX_OK;
+}
+int dist_set_source(mgx_ctx *c, const double *f, hipMemcpyKind kind) {
+    Dist *d = c->dist;
+    HIPCHK(hipSetDevice(c->device));
+    CHK(settle(c));
+    dist_set_source_scale(c, c->src_scale);   // drops the speculative states
+    if (d->la == 0) {
+        int rc = MGX_OK;
+        for (auto &p : d->parts)
+            if (rc == MGX_OK) rc = set_source_ctx(p.sub, f, kind);
+        if (rc != MGX_OK)   // all parts or none
+            for (auto &p : d->parts) (void)set_source_ctx(p.sub, nullptr, kind);
+        c->src_active = rc == MGX_OK && f;
+        c->src_terms = 0;   // (set_source_ctx dropped a separable source)
+        return rc;
+    }
+    if (!f) {
+        HIPCHK(hipStreamSynchronize(c->stream));   // a pass may still read the copies
+        free_sources(c);
+        free_source_factors(c);
+        return MGX_OK;
+    }
+    return set_source_blocks(c, [&](Part &p) { return f + (long)p.lv[0].ra * (c->N + 1); }, kind);
+}
+int dist_set_source_rows(mgx_ctx *c, const double *const *f, hipMemcpyKind kind) {
+    Dist *d = c->dist;
+    HIPCHK(hipSetDevice(c->device));
+    CHK(settle(c));
+    dist_set_source_scale(c, c->src_scale);   // drops the speculative states
+    return set_source_blocks(c, [&](Part &p) { return f[&p - d->parts.data()]; }, kind);
+}
+// mgx_set_source_separable on a partitioned context: every part keeps b and
+// all of a (8(N+1) bytes per vector), the replicated sub-contexts of a fully
+// replicated context likewise.  No communication: RCCL ranks pass the same
+// values.  All parts or none.
+int dist_set_source_sep(mgx_ctx *c, int terms, const double *a, const double *b,
+                        hipMemcpyKind kind) {
+    Dist *d = c->dist;
+    HIPCHK(hipSetDevice(c->device));
+    CHK(settle(c));
+    dist_set_source_scale(c, c->src_scale);   // drops the speculative states
+    int rc = MGX_OK;
+    if (d->la == 0) {
+        for (auto &p : d->parts)
+            if (rc == MGX_OK) rc = set_source_sep_ctx(p.sub, terms, a, b, kind);
+        if (rc != MGX_OK)
+            for (auto &p : d->parts) (void)set_source_ctx(p.sub, nullptr, kind);
+        c->src_active = rc == MGX_OK;
+        c->src_terms = rc == MGX_OK ? terms : 0;
+        return rc;
+    }
+    if (c->src_active && !c->src_terms) {   // one source per context: the field copies go
+        HIPCHK(hipStreamSynchronize(c->stream));
+        free_sources(c);
+    }
+    for (auto &p : d->parts) {
+        PLevel &L = p.lv[0];
+        if (rc == MGX_OK)
+            rc = copy_source_factors(&L.src_a, &L.src_b, L.n, L.pitch, terms, a, b, kind,
+                                     c->stream, "mgx_set_source_separable");
+    }
+    if (hipStreamSynchronize(c->stream) != hipSuccess && rc == MGX_OK)
+        rc = fail(MGX_E_HIP, "mgx_set_source_separable: copy");
+    if (rc != MGX_OK) {   // all parts or none
+        free_source_factors(c);
+        c->src_active = false;
+        return rc;
+    }
+    for (auto &p : d->parts) p.lv[0].src_terms = terms;
+    c->src_terms = terms;
     c->src_active = true;
     return MGX_OK;
 }
@@ -1409,6 +1496,7 @@ int dist_download_rows(mgx_ctx *c, int part, double *out, hipMemcpyKind kind) {
 // local part `part` as a view, and the part's owned rows.  With every level
 // replicated it is the part's full copy in its sub-context.  Host checks
 // first; the only device call is the sub-context's materialize.
+static const char *const kSepNoCopy = ": the source is separable: no copy of it is kept (field 4)";
 static int part_view(mgx_ctx *c, int part, int field, const char *who, mgxdiag::View *v, int *ra,
                      int *rb) {
     Dist *d = c->dist;
@@ -1419,10 +1507,12 @@ static int part_view(mgx_ctx *c, int part, int field, const char *who, mgxdiag::
     plan_rows(c->N, 0, d->world, d->parts[part].rank, ra, rb);
     if (d->la == 0) {
         mgx_ctx *s = d->parts[part].sub;
+        if (field == 4 && s->src_terms) return fail(MGX_E_ARG, std::string(who) + kSepNoCopy);
         if (field == 4 && !s->src) return fail(MGX_E_ARG, std::string(who) + ": no source is set");
         return field_view(s, 0, field, v);
     }
     PLevel &L = d->parts[part].lv[0];
+    if (field == 4 && L.src_terms) return fail(MGX_E_ARG, std::string(who) + kSepNoCopy);
     if (field == 4 && !L.src) return fail(MGX_E_ARG, std::string(who) + ": no source is set");
     v->a = field == 0 ? L.u[L.cur] : field == 1 ? L.rhs : field == 2 ? L.v1 : field == 3 ? L.v2
                                                                                          : L.src;
@@ -1455,6 +1545,8 @@ int dist_field_stats(mgx_ctx *c, int level, int field, int interior, const doubl
                                "context");
     if (field < 0 || field > 4)
         return fail(MGX_E_ARG, "mgx_field_stats: field must be 0..4 (u, rhs, v1, v2, source)");
+    if (field == 4 && c->src_active && c->src_terms)
+        return fail(MGX_E_ARG, std::string(who) + kSepNoCopy);
     if (field == 4 && !c->src_active) return fail(MGX_E_ARG, "mgx_field_stats: no source is set");
     HIPCHK(hipSetDevice(c->device));
     CHK(settle(c));
@@ -1503,6 +1595,8 @@ int dist_sample(mgx_ctx *c, int level, int field, long stride, double *out, bool
                                                   "context");
     if (field < 0 || field > 4)
         return fail(MGX_E_ARG, std::string(who) + ": field must be 0..4 (u, rhs, v1, v2, source)");
+    if (field == 4 && c->src_active && c->src_terms)
+        return fail(MGX_E_ARG, std::string(who) + kSepNoCopy);
     if (field == 4 && !c->src_active) return fail(MGX_E_ARG, std::string(who) + ": no source is set");
     CHK(check_stride(c->N, stride, who));
     HIPCHK(hipSetDevice(c->device));
@@ -1531,6 +1625,8 @@ int dist_sample_rows(mgx_ctx *c, int part, int field, long stride, double *out, 
         return fail(MGX_E_ARG, "mgx_sample_rows: bad part");
     if (field < 0 || field > 4)
         return fail(MGX_E_ARG, "mgx_sample_rows: field must be 0..4 (u, rhs, v1, v2, source)");
+    if (field == 4 && c->src_active && c->src_terms)
+        return fail(MGX_E_ARG, std::string(who) + kSepNoCopy);
     if (field == 4 && !c->src_active) return fail(MGX_E_ARG, "mgx_sample_rows: no source is set");
     CHK(check_stride(c->N, stride, who));
     SamplePiece s;

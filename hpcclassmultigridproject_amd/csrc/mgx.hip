@@ -767,6 +767,9 @@ static mgxsrc::SrcArgs source_args(mgx_ctx *c, bool norm, double *cbytes) {
     A.v1 = L.v1;
     A.v2 = L.v2;
     A.f = c->src;
+    A.terms = c->src_terms;   // > 0: the separable form, no f stream
+    A.fa = c->src_a;
+    A.fb = c->src_b;
     A.cf = c->dt * c->src_scale;
     A.n = L.n;
     A.pitch = L.pitch;
@@ -782,7 +785,8 @@ static mgxsrc::SrcArgs source_args(mgx_ctx *c, bool norm, double *cbytes) {
         A.partials = c->partials;
         A.norm_out = c->dscal;
     }
-    *cbytes = (sv ? 24.0 : 40.0) * L.M();   // u, f, rhs (+ v1, v2)
+    // u, rhs (+ f unless separable) (+ v1, v2)
+    *cbytes = ((sv ? 16.0 : 32.0) + (A.terms ? 0.0 : 8.0)) * L.M();
     return A;
 }
 
@@ -790,10 +794,10 @@ int op_rhs(mgx_ctx *c) {
     drop_spec(c);
     CHK(materialize(c, 0));
     Level &L = c->lv[0];
-    if (c->src) {   // compute_rhs 32 B per point + the f stream
+    if (c->has_source()) {   // compute_rhs 32 B per point + the f stream of a field
         double cb = 0;
         const mgxsrc::SrcArgs A = source_args(c, false, &cb);
-        return launch(c, MGX_K_RHS, 0, 40.0 * L.M(), cb,
+        return launch(c, MGX_K_RHS, 0, (A.terms ? 32.0 : 40.0) * L.M(), cb,
                       [&] { mgxsrc::launch_rhs_source(A, c->stream); });
     }
     return launch(c, MGX_K_RHS, 0, 32.0 * L.M(), [&] {
@@ -807,10 +811,10 @@ static int op_rhs_norm(mgx_ctx *c, double *res0) {
     drop_spec(c);
     CHK(materialize(c, 0));
     Level &L = c->lv[0];
-    if (c->src) {
+    if (c->has_source()) {
         double cb = 0;
         const mgxsrc::SrcArgs A = source_args(c, true, &cb);
-        CHK(launch(c, MGX_K_RHS, 0, 40.0 * L.M() + 48.0 * L.M(), cb,
+        CHK(launch(c, MGX_K_RHS, 0, (A.terms ? 32.0 : 40.0) * L.M() + 48.0 * L.M(), cb,
                    [&] { mgxsrc::launch_rhs_source(A, c->stream); }));
         return read_norm(c, res0);
     }
@@ -1123,6 +1127,8 @@ void free_ctx(mgx_ctx *c) {
     (void)hipFree(c->zrow);
     (void)hipFree(c->vga);
     (void)hipFree(c->src);
+    (void)hipFree(c->src_a);
+    (void)hipFree(c->src_b);
     (void)hipFree(c->diag);
     if (c->hscal) (void)hipHostFree(c->hscal);
     for (auto &r : c->pending) {
@@ -1429,6 +1435,14 @@ int mgxi::set_source_ctx(mgx_ctx *c, const double *f, hipMemcpyKind kind) {
     HIPCHK(hipSetDevice(c->device));
     drop_source_state(c);
     Level &L = c->lv[0];
+    if (c->src_terms) {   // one source per context: the separable one goes
+        HIPCHK(hipStreamSynchronize(c->stream));   // a pass may still read the factors
+        (void)hipFree(c->src_a);
+        (void)hipFree(c->src_b);
+        c->src_a = c->src_b = nullptr;
+        c->src_terms = 0;
+        c->src_active = false;
+    }
     if (!f) {
         if (c->src) {
             HIPCHK(hipStreamSynchronize(c->stream));   // a pass may still read it
@@ -1458,6 +1472,84 @@ int mgxi::set_source_ctx(mgx_ctx *c, const double *f, hipMemcpyKind kind) {
     HIPCHK(hipStreamSynchronize(c->stream));   // the caller's buffer is free on return
     c->src_active = true;
     return MGX_OK;
+}
+
+// The device copies of separable factors: a -> terms rows of n+1, b -> terms
+// rows of `pitch` (the pad zeroed once, at allocation; the copies write n+1
+// entries per row).  Both buffers are sized for MGX_SOURCE_MAX_TERMS, so a
+// replacement with another term count reuses them.
+int mgxi::copy_source_factors(double **da, double **db, long n, long pitch, int terms,
+                              const double *a, const double *b, hipMemcpyKind kind,
+                              hipStream_t s, const char *who) {
+    const size_t abytes = sizeof(double) * (size_t)MGX_SOURCE_MAX_TERMS * (size_t)(n + 1);
+    const size_t bbytes = sizeof(double) * (size_t)MGX_SOURCE_MAX_TERMS * (size_t)pitch;
+    double **dst[2] = {da, db};
+    const size_t bytes[2] = {abytes, bbytes};
+    for (int k = 0; k < 2; ++k) {
+        if (*dst[k]) continue;
+        const hipError_t e = hipMalloc(dst[k], bytes[k]);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            *dst[k] = nullptr;
+            return fail(MGX_E_HIP, std::string(who) + ": no room for the factors: " +
+                                       hipGetErrorString(e));
+        }
+        HIPCHK(hipMemsetAsync(*dst[k], 0, bytes[k], s));
+    }
+    const size_t row = (size_t)(n + 1) * sizeof(double);
+    HIPCHK(hipMemcpyAsync(*da, a, row * terms, kind, s));
+    HIPCHK(hipMemcpy2DAsync(*db, pitch * sizeof(double), b, row, row, terms, kind, s));
+    return MGX_OK;
+}
+
+// mgx_set_source_separable on a single-GPU context: no finest-level array
+int mgxi::set_source_sep_ctx(mgx_ctx *c, int terms, const double *a, const double *b,
+                             hipMemcpyKind kind) {
+    HIPCHK(hipSetDevice(c->device));
+    drop_source_state(c);
+    Level &L = c->lv[0];
+    if (c->src) {   // one source per context: the field copy goes
+        HIPCHK(hipStreamSynchronize(c->stream));   // a pass may still read it
+        (void)hipFree(c->src);
+        c->src = nullptr;
+    }
+    const int rc = copy_source_factors(&c->src_a, &c->src_b, L.n, L.pitch, terms, a, b, kind,
+                                       c->stream, "mgx_set_source_separable");
+    if (rc != MGX_OK || hipStreamSynchronize(c->stream) != hipSuccess) {
+        (void)hipGetLastError();
+        c->src_terms = 0;
+        c->src_active = false;
+        return rc != MGX_OK ? rc : fail(MGX_E_HIP, "mgx_set_source_separable: copy");
+    }
+    c->src_terms = terms;   // (the caller's buffers are free on return)
+    c->src_active = true;
+    return MGX_OK;
+}
+
+static int set_source_sep_impl(mgx_ctx *c, int terms, const double *a, const double *b,
+                               hipMemcpyKind kind, const char *who) {
+    if (!c) return fail(MGX_E_ARG, std::string(who) + ": null ctx");
+    if (terms < 1 || terms > MGX_SOURCE_MAX_TERMS)
+        return fail(MGX_E_ARG, std::string(who) + ": terms must be 1.." +
+                                   std::to_string(MGX_SOURCE_MAX_TERMS));
+    if (!a || !b) return fail(MGX_E_ARG, std::string(who) + ": null factors");
+    if (c->dist) return dist_set_source_sep(c, terms, a, b, kind);
+    return set_source_sep_ctx(c, terms, a, b, kind);
+}
+
+static int set_source_rows_impl(mgx_ctx *c, const double *const *f, hipMemcpyKind kind,
+                                const char *who) {
+    if (!c) return fail(MGX_E_ARG, std::string(who) + ": null ctx");
+    if (!f) return fail(MGX_E_ARG, std::string(who) + ": null block list");
+    const int parts = c->dist ? dist_nsub(c) : 1;
+    for (int i = 0; i < parts; ++i)
+        if (!f[i]) return fail(MGX_E_ARG, std::string(who) + ": null block");
+    if (c->dist) {
+        if (dist_la(c) == 0)
+            return fail(MGX_E_ARG, std::string(who) + ": no partitioned level, use mgx_set_source");
+        return dist_set_source_rows(c, f, kind);
+    }
+    return set_source_ctx(c, f[0], kind);   // part 0 is all rows
 }
 
 static int set_source_impl(mgx_ctx *c, const double *f, hipMemcpyKind kind, const char *who) {
@@ -1490,6 +1582,38 @@ int mgx_source_info(mgx_ctx *c, int *active, double *scale) {
     if (active) *active = c->src_active ? 1 : 0;
     if (scale) *scale = c->src_scale;
     return MGX_OK;
+}
+int mgx_set_source_separable(mgx_ctx *c, int terms, const double *a, const double *b) {
+    return set_source_sep_impl(c, terms, a, b, hipMemcpyHostToDevice, "mgx_set_source_separable");
+}
+int mgx_set_source_separable_device(mgx_ctx *c, int terms, const double *a, const double *b) {
+    return set_source_sep_impl(c, terms, a, b, hipMemcpyDeviceToDevice,
+                               "mgx_set_source_separable_device");
+}
+int mgx_set_source_rows(mgx_ctx *c, const double *const *f) {
+    return set_source_rows_impl(c, f, hipMemcpyHostToDevice, "mgx_set_source_rows");
+}
+int mgx_set_source_rows_device(mgx_ctx *c, const double *const *f) {
+    return set_source_rows_impl(c, f, hipMemcpyDeviceToDevice, "mgx_set_source_rows_device");
+}
+int mgx_source_kind(mgx_ctx *c, int *kind, int *terms) {
+    if (!c) return fail(MGX_E_ARG, "mgx_source_kind: null ctx");
+    if (kind) *kind = !c->src_active ? 0 : c->src_terms ? 2 : 1;
+    if (terms) *terms = c->src_active ? c->src_terms : 0;
+    return MGX_OK;
+}
+int mgx_compute_rhs_source_separable(double *rhs, const double *u, long n, const double *v1,
+                                     const double *v2, double k, double nu, double h, int terms,
+                                     const double *a, const double *b, double cf) {
+    if (!rhs || !u || !v1 || !v2 || !a || !b)
+        return fail(MGX_E_ARG, "mgx_compute_rhs_source_separable: null pointer");
+    if (n < 2) return fail(MGX_E_ARG, "mgx_compute_rhs_source_separable: n must be >= 2");
+    if (terms < 1 || terms > MGX_SOURCE_MAX_TERMS)
+        return fail(MGX_E_ARG, "mgx_compute_rhs_source_separable: terms must be 1.." +
+                                   std::to_string(MGX_SOURCE_MAX_TERMS));
+    mgxsrc::launch_raw_rhs_source_sep(rhs, u, v1, v2, terms, a, b, cf, n,
+                                      mgx::make_coef(k, nu, h), nullptr);
+    return check_launch("mgx_compute_rhs_source_separable");
 }
 int mgx_compute_rhs_source(double *rhs, const double *u, long n, const double *v1,
                            const double *v2, double k, double nu, double h, const double *f,
@@ -1623,6 +1747,9 @@ static int field_check(mgx_ctx *c, int level, int field, const char *who) {
         return fail(MGX_E_ARG, std::string(who) + ": level out of range");
     if (field < 0 || field > 4)
         return fail(MGX_E_ARG, std::string(who) + ": field must be 0..4 (u, rhs, v1, v2, source)");
+    if (field == 4 && level == 0 && c->src_terms)
+        return fail(MGX_E_ARG, std::string(who) + ": the source is separable: no copy of it is "
+                                                  "kept (field 4)");
     if (field == 4 && (level != 0 || !c->src))
         return fail(MGX_E_ARG, std::string(who) + ": no source is set (field 4 is the context's "
                                                   "copy of it, level 0)");
@@ -1689,6 +1816,9 @@ int mgx_field_stats_rows(mgx_ctx *c, int part, int field, int interior_only,
                          const double *minus_rows, mgx_stats *out) {
     if (!c || !out) return fail(MGX_E_ARG, "mgx_field_stats_rows: null argument");
     if (c->dist) {
+        if (field == 4 && c->src_active && c->src_terms)
+            return fail(MGX_E_ARG, "mgx_field_stats_rows: the source is separable: no copy of "
+                                   "it is kept (field 4)");
         if (field == 4 && !c->src_active)
             return fail(MGX_E_ARG, "mgx_field_stats_rows: no source is set");
         mgxdiag::timer_reset();
@@ -1837,7 +1967,7 @@ static int step_impl(mgx_ctx *c, double tol, int *cycles, bool prepare_next,
         c->step_spec = false;   // lv[0].spec and lv[1]'s rhs stay: the first cycle's
     } else if (c->dist) {
         CHK(dist_rhs_norm(c, &res0));
-    } else if (!c->src && step_fusable(c)) {
+    } else if (!c->has_source() && step_fusable(c)) {
         CHK(op_rhs_norm_pre(c, &res0));
     } else {
         CHK(op_rhs_norm(c, &res0));
@@ -1845,7 +1975,7 @@ static int step_impl(mgx_ctx *c, double tol, int *cycles, bool prepare_next,
     // (a source: both fused forms make the rhs inside kernels that know none --
     // k_wsmooth's kModeRhsNorm above, the cross pass's step mode here)
     c->step_next =
-        prepare_next && g_step_cross != 0 && !c->dist && !c->src && step_rhs_alt(c);
+        prepare_next && g_step_cross != 0 && !c->dist && !c->has_source() && step_rhs_alt(c);
     const int rc = op_mg_outer(c, tol, cycles, res0_out, res_out, &res0);
     c->step_next = false;
     return rc;

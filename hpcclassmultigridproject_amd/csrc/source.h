@@ -9,6 +9,14 @@
 // v1, v2, f in, rhs out, optionally the sum of squares of rhs - A u.  The norm
 // instance uses k_res_march<0>'s grid and partial-sum order, so the norm is
 // bitwise launch_residual_norm's on the stored rhs.
+//
+// A separable source (mgx_set_source_separable) is a short sum of outer
+// products given by its factors, 1 <= R <= kMaxTerms terms:
+//     f(i,j) = fl( ... fl( fl(t_0 + t_1) + t_2 ) ... ),  t_r = fl(a[r][i] * b[r][j])
+// (f = t_0 for R = 1), left to right, every product and sum rounded: bitwise
+// the array numpy builds with f = a[0][:,None]*b[0][None,:], then f = f +
+// a[r][:,None]*b[r][None,:].  The march forms it in registers: no array, no
+// stream, and the norm instance is bitwise that of the field pass on that f.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -16,10 +24,17 @@
 
 namespace mgxsrc {
 
+constexpr int kMaxTerms = 4;   // MGX_SOURCE_MAX_TERMS
+
 struct SrcArgs {
     double *rhs = nullptr;
     const double *u = nullptr, *v1 = nullptr, *v2 = nullptr;
     const double *f = nullptr;   // the source, tower layout (ptr + r*pitch = global row r)
+    // terms > 0: a separable source instead of f.  fa + r*(n+1): the row factor
+    // of term r, indexed by the global row; fb + r*pitch: its column factor,
+    // zero padded to the pitch
+    int terms = 0;
+    const double *fa = nullptr, *fb = nullptr;
     double cf = 0.0;             // fl(dt * scale)
     long n = 0, pitch = 0;
     mgx::Coef c{};
@@ -39,5 +54,9 @@ void launch_rhs_source(const SrcArgs &a, hipStream_t s);
 // reference layout (pitch n+1, one point per lane), the gs.h-style raw op
 void launch_raw_rhs_source(double *rhs, const double *u, const double *v1, const double *v2,
                            const double *f, double cf, long n, mgx::Coef c, hipStream_t s);
+// the same with a separable source: fa, fb hold terms x (n+1) doubles, term-major
+void launch_raw_rhs_source_sep(double *rhs, const double *u, const double *v1, const double *v2,
+                               int terms, const double *fa, const double *fb, double cf, long n,
+                               mgx::Coef c, hipStream_t s);
 
 }  // namespace mgxsrc

@@ -30,13 +30,27 @@ namespace {
 //                 column factors stay in registers for the whole march, the
 //                 row factors are wave-uniform (scalar) loads.  u, f in and
 //                 rhs out are the pass's only full streams.
-template <bool NORM, bool SV>
-__global__ __launch_bounds__(256) void k_rhs_source(
+//   SF = 0:       f is a finest-level array (one more full stream);
+//   SF = 1..4:    f is a separable source of SF terms (source.h): the lane
+//                 forms its column pair of f in registers,
+//                     f = t_0 (+ t_1 (+ t_2 (+ t_3))) left to right,
+//                     t_r = fl(fa[r][i] * fb[r][j]),
+//                 each product and each sum rounded (no contraction), so f is
+//                 bitwise the array numpy builds from the factors.  The fb
+//                 pairs of the lane's two columns stay in registers for the
+//                 whole march like sb1 / sb2 (fb[r] = fb + r*pitch, zero
+//                 padded; one instance keeps two of them in LDS: HOLD below),
+//                 the fa[r][i] (fa + r*(n+1)) are wave-uniform loads per row
+//                 like sa1[i].  No f stream.  (waves_per_eu 8: every instance
+//                 within the 64 VGPRs of 8 waves per SIMD, none with scratch.)
+template <bool NORM, bool SV, int SF>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void k_rhs_source(
     const double *__restrict__ u, const double *__restrict__ v1, const double *__restrict__ v2,
     const double *__restrict__ sa1, const double *__restrict__ sb1,
     const double *__restrict__ sa2, const double *__restrict__ sb2,
-    const double *__restrict__ f, double cf, int n, long pitch, Coef c, int rows_per_group,
-    double *__restrict__ out, double *__restrict__ partials, int r_first, int r_end) {
+    const double *__restrict__ f, const double *__restrict__ fa, const double *__restrict__ fb,
+    double cf, int n, long pitch, Coef c, int rows_per_group, double *__restrict__ out,
+    double *__restrict__ partials, int r_first, int r_end) {
     __shared__ double lds[4];
     const int t = threadIdx.x, lane = t & 63;
     const long c0 = (long)blockIdx.x * 512 + 2 * t;
@@ -47,6 +61,18 @@ __global__ __launch_bounds__(256) void k_rhs_source(
     const double2 z2 = make_double2(0.0, 0.0);
     double2 un = z2, um = z2, us = z2;
     double2 b1 = z2, b2 = z2;
+    // the separable source's column factors: HOLD of them stay in registers
+    // for the whole march -- all of them, except in the one instance that would
+    // not fit the 64 VGPRs of 8 waves per SIMD (norm + velocity factors + four
+    // terms: 70 VGPRs holding all).  That one holds two in registers and the
+    // other two in LDS, a private slot per lane (written once before the
+    // march, read back per row by the lane that wrote it: no barrier).
+    constexpr int HOLD = (NORM && SV && SF > 3) ? 2 : SF;
+    constexpr int OVER = SF - HOLD;
+    __shared__ double2 gl[(OVER > 0 ? OVER : 1) * 256];
+    double2 g[SF > 0 ? SF : 1];
+#pragma unroll
+    for (int r = 0; r < SF; ++r) g[r] = z2;
     if (act && i0 < i1) {
         un = ld2(u + (i0 - 1) * pitch + c0);
         um = ld2(u + i0 * pitch + c0);
@@ -54,13 +80,29 @@ __global__ __launch_bounds__(256) void k_rhs_source(
             b1 = ld2(sb1 + c0);
             b2 = ld2(sb2 + c0);
         }
+#pragma unroll
+        for (int r = 0; r < HOLD; ++r) g[r] = ld2(fb + r * pitch + c0);
+#pragma unroll
+        for (int r = HOLD; r < SF; ++r) gl[(r - HOLD) * 256 + t] = ld2(fb + r * pitch + c0);
     }
     for (long i = i0; i < i1; ++i) {
         const long o = i * pitch;
         double2 x2 = z2, y2 = z2, s2 = z2;
         if (act) {
             us = ld2(u + o + pitch + c0);
-            s2 = ld2s(f + o + c0);   // touched once per step
+            if (SF > 0) {
+                const double a0 = fa[i];
+                s2 = make_double2(a0 * g[0].x, a0 * g[0].y);
+#pragma unroll
+                for (int r = 1; r < SF; ++r) {
+                    const double ar = fa[r * (long)(n + 1) + i];
+                    const double2 gr = r < HOLD ? g[r] : gl[(r - HOLD) * 256 + t];
+                    const double tx = ar * gr.x, ty = ar * gr.y;
+                    s2 = make_double2(s2.x + tx, s2.y + ty);
+                }
+            } else {
+                s2 = ld2s(f + o + c0);   // touched once per step
+            }
             if (SV) {
                 const double a1 = sa1[i], a2 = sa2[i];
                 x2 = make_double2(a1 * b1.x, a1 * b1.y);
@@ -121,6 +163,28 @@ __global__ __launch_bounds__(256) void k_raw_rhs_source(double *rhs, const doubl
     }
 }
 
+// the same with a separable source: fa, fb are terms x (n+1), term-major
+__global__ __launch_bounds__(256) void k_raw_rhs_source_sep(double *rhs, const double *u,
+                                                            const double *v1, const double *v2,
+                                                            int terms, const double *fa,
+                                                            const double *fb, double cf, long n,
+                                                            Coef c) {
+    const long w = n + 1;
+    const long j = 1 + (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    for (long i = 1 + blockIdx.y; i < n; i += gridDim.y) {
+        const long p = i * w + j;
+        const double b = rhs_point(v1[p], v2[p], u[p], u[p - w], u[p - 1], u[p + w], u[p + 1], c);
+        double f = fa[i] * fb[j];
+        for (int r = 1; r < terms; ++r) {
+            const double t = fa[r * w + i] * fb[r * w + j];
+            f = f + t;
+        }
+        const double s = cf * f;
+        rhs[p] = b + s;
+    }
+}
+
 // kernels.hip's res_grid: the grid of every k_res_march launch (the norm
 // instance must cut the rows exactly as launch_residual_norm does)
 void res_grid(long n, long rows, dim3 &g, int &R) {
@@ -131,10 +195,21 @@ void res_grid(long n, long rows, dim3 &g, int &R) {
     g = dim3(strips, cdiv(rows, R));
 }
 
-template <bool NORM, bool SV>
+template <bool NORM, bool SV, int SF>
 void launch_inst(const SrcArgs &a, dim3 g, int R, int f, int e, hipStream_t s) {
-    MGX_LAUNCH((k_rhs_source<NORM, SV>), g, dim3(256), s, a.u, a.v1, a.v2, a.sa1, a.sb1, a.sa2,
-               a.sb2, a.f, a.cf, (int)a.n, a.pitch, a.c, R, a.rhs, a.partials, f, e);
+    MGX_LAUNCH((k_rhs_source<NORM, SV, SF>), g, dim3(256), s, a.u, a.v1, a.v2, a.sa1, a.sb1, a.sa2,
+               a.sb2, a.f, a.fa, a.fb, a.cf, (int)a.n, a.pitch, a.c, R, a.rhs, a.partials, f, e);
+}
+// the instance of the source's form: a field (terms 0) or 1..4 separable terms
+template <bool NORM, bool SV>
+void launch_form(const SrcArgs &a, dim3 g, int R, int f, int e, hipStream_t s) {
+    switch (a.terms) {
+        case 0: launch_inst<NORM, SV, 0>(a, g, R, f, e, s); break;
+        case 1: launch_inst<NORM, SV, 1>(a, g, R, f, e, s); break;
+        case 2: launch_inst<NORM, SV, 2>(a, g, R, f, e, s); break;
+        case 3: launch_inst<NORM, SV, 3>(a, g, R, f, e, s); break;
+        default: launch_inst<NORM, SV, 4>(a, g, R, f, e, s); break;
+    }
 }
 
 }  // namespace
@@ -153,15 +228,15 @@ void launch_rhs_source(const SrcArgs &a, hipStream_t s) {
     const bool norm = a.partials != nullptr;
     if (norm) {
         if (sv)
-            launch_inst<true, true>(a, g, R, f, e, s);
+            launch_form<true, true>(a, g, R, f, e, s);
         else
-            launch_inst<true, false>(a, g, R, f, e, s);
+            launch_form<true, false>(a, g, R, f, e, s);
         launch_norm_final(a.partials, (int)(g.x * g.y), a.norm_out, a.take_sqrt ? 1 : 0, s);
     } else {
         if (sv)
-            launch_inst<false, true>(a, g, R, f, e, s);
+            launch_form<false, true>(a, g, R, f, e, s);
         else
-            launch_inst<false, false>(a, g, R, f, e, s);
+            launch_form<false, false>(a, g, R, f, e, s);
     }
 }
 
@@ -172,6 +247,15 @@ void launch_raw_rhs_source(double *rhs, const double *u, const double *v1, const
     const unsigned gy = (unsigned)std::max<long>(1, std::min<long>(n - 1, 32768));
     MGX_LAUNCH(k_raw_rhs_source, dim3(cdiv(n - 1, 256), gy), dim3(256), s, rhs, u, v1, v2, f, cf, n,
                c);
+}
+
+void launch_raw_rhs_source_sep(double *rhs, const double *u, const double *v1, const double *v2,
+                               int terms, const double *fa, const double *fb, double cf, long n,
+                               Coef c, hipStream_t s) {
+    if (n < 2 || terms < 1 || terms > kMaxTerms) return;
+    const unsigned gy = (unsigned)std::max<long>(1, std::min<long>(n - 1, 32768));
+    MGX_LAUNCH(k_raw_rhs_source_sep, dim3(cdiv(n - 1, 256), gy), dim3(256), s, rhs, u, v1, v2,
+               terms, fa, fb, cf, n, c);
 }
 
 }  // namespace mgxsrc

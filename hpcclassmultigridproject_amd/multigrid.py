@@ -175,6 +175,72 @@ class Multigrid:
                 raise ValueError("f must be a contiguous float64 tensor of (N+1)^2 entries")
             check(lib().mgx_set_source_device(self._h, f.data_ptr()))
 
+    def set_source_separable(self, a, b):
+        """A source given by its factors (mgx_set_source_separable): f(i,j) =
+        a[0][i]*b[0][j] (+ a[1][i]*b[1][j] ...), each product rounded and the
+        terms added left to right -- bit for bit set_source() of that array,
+        with no finest-level array kept and no source stream read.  a (rows)
+        and b (columns): 1-D arrays of N+1 for one term or (R, N+1) arrays, R
+        <= 4; numpy arrays, or torch tensors on the solver's device.  Replaces
+        a source of either kind; calling it again replaces the factors in
+        place (a moving emitter: one call per step).  Every kind of solver
+        takes it; RCCL ranks must all pass the same values."""
+        host = isinstance(a, np.ndarray)
+        if host != isinstance(b, np.ndarray):
+            raise ValueError("a and b must both be numpy arrays or both device tensors")
+        sa, sb = tuple(a.shape), tuple(b.shape)
+        if sa != sb or len(sa) not in (1, 2) or sa[-1] != self.N + 1:
+            raise ValueError("a and b must both have shape (N+1,) or (R, N+1)")
+        terms = 1 if len(sa) == 1 else sa[0]
+        if not 1 <= terms <= _lib.MGX_SOURCE_MAX_TERMS:
+            raise ValueError(f"a separable source has 1..{_lib.MGX_SOURCE_MAX_TERMS} terms")
+        if host:
+            check(lib().mgx_set_source_separable(self._h, terms, _np_ptr(a), _np_ptr(b)))
+        else:
+            for x in (a, b):
+                if x.element_size() != 8 or not x.is_contiguous():
+                    raise ValueError("a, b must be contiguous float64 tensors")
+            check(lib().mgx_set_source_separable_device(self._h, terms, a.data_ptr(),
+                                                        b.data_ptr()))
+
+    def set_source_rows(self, blocks):
+        """Row-block set_source (mgx_set_source_rows) for solvers on which
+        nobody holds the whole grid: blocks[i] = the source on the OWNED rows
+        [ra, rb) (owned_rows) of local part i, (rb-ra)*(N+1) float64, all numpy
+        arrays or all device tensors.  Needs a partitioned level (dist_info);
+        on a single-GPU solver the one block is the whole grid."""
+        blocks = list(blocks)
+        host = all(isinstance(x, np.ndarray) for x in blocks)
+        if not host and any(isinstance(x, np.ndarray) for x in blocks):
+            raise ValueError("blocks must all be numpy arrays or all device tensors")
+        world, rank, _ = self.dist_info()
+        parts = world if rank < 0 else 1
+        if len(blocks) != parts:
+            raise ValueError(f"expected {parts} blocks, one per local part")
+        ptrs = []
+        for i, x in enumerate(blocks):
+            ra, rb = self.owned_rows(i)
+            cnt = (rb - ra) * (self.N + 1)
+            if host:
+                if x.size != cnt:
+                    raise ValueError(f"block {i} must hold {cnt} doubles")
+                ptrs.append(_np_ptr(x))
+            else:
+                if x.numel() != cnt or x.element_size() != 8 or not x.is_contiguous():
+                    raise ValueError(f"block {i} must be a contiguous float64 tensor of {cnt} "
+                                     "entries")
+                ptrs.append(x.data_ptr())
+        arr =(C.c_void_p * len(ptrs))(*ptrs)
+        f = lib().mgx_set_source_rows if host else lib().mgx_set_source_rows_device
+        check(f(self._h, arr))
+
+    def source_kind(self):
+        """-> (kind, terms) (mgx_source_kind): kind 0 none, 1 field (whole grid
+        or row blocks), 2 separable; terms: R of a separable source, else 0."""
+        k, t = C.c_int(), C.c_int()
+        check(lib().mgx_source_kind(self._h, C.byref(k), C.byref(t)))
+        return k.value, t.value
+
     def set_source_scale(self, s):
         """The factor s of the source term fl(dt * s) * f (default 1): a
         time-separable source g(t) f(x, y) needs no new upload per step."""

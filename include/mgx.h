@@ -482,8 +482,55 @@ int mgx_set_velocity_device(mgx_ctx *ctx, const double *v1, const double *v2);
  *
  * Partitioned contexts (mgx_create_local_dist, mgx_create_dist) take the
  * whole-grid calls: each part keeps its owned rows, and no exchange is added
- * (the term is pointwise).  A row-block counterpart for contexts filled with
- * mgx_upload_rows (no rank holds the whole grid) does not exist yet. */
+ * (the term is pointwise).
+ *
+ * Separable and row-block sources.  A context has ONE source: a field (set by
+ * mgx_set_source or, row block by row block, by mgx_set_source_rows) or a
+ * separable one (mgx_set_source_separable).  Setting either kind replaces the
+ * other and frees a field copy; mgx_set_source(ctx, NULL) removes whichever is
+ * set.  The scale, the survival across mgx_upload* and mgx_set_velocity*, the
+ * dropped state and mgx_source_info (active = 1 for either kind) are those
+ * described above; mgx_source_kind tells the kinds apart.
+ *
+ * mgx_set_source_separable[_device]: the source is a short sum of outer
+ * products, 1 <= terms <= MGX_SOURCE_MAX_TERMS, given by its factors a[r][0..N]
+ * (rows) and b[r][0..N] (columns), term-major:
+ *     f(i,j) = t_0                                  for one term,
+ *     f(i,j) = fl( ... fl( fl(t_0 + t_1) + t_2 ) ... )   left to right,
+ *     t_r    = fl( a[r][i] * b[r][j] ),
+ * then rhs = fl(Bu + fl(c * f)) as above, never contracted: bit for bit what
+ * mgx_set_source gives for the array built in that order (numpy: f =
+ * a[0][:,None]*b[0][None,:], then f = f + a[r][:,None]*b[r][None,:]).
+ * Boundary entries of a and b are ignored.  The pass forms f in registers: no
+ * finest-level array is allocated (the call cannot fail for room at N=65536),
+ * no f stream is read, and mg_outer's initial norm is bitwise that of the
+ * field pass on the same f.  The context keeps its own copies of the factors
+ * (8(N+1) bytes per vector); replacing the factors of a separable source that
+ * is set reuses them -- the per-step call of a moving emitter, about 1 MB at
+ * N=16384 with four terms.  It works on every kind of context: a single GPU,
+ * local parts and RCCL ranks, filled by mgx_upload or mgx_upload_rows; every
+ * part keeps the factors and no exchange is added.  On RCCL ranks every rank
+ * must pass the same values: the call does not communicate, so a mismatch
+ * cannot hang -- it gives a right-hand side no single source describes.
+ * Field 4 of mgx_field_stats* / mgx_sample* returns MGX_E_ARG on a separable
+ * source (no copy of f is kept).
+ *
+ * mgx_set_source_rows[_device]: the row-block counterpart of mgx_set_source for
+ * contexts on which no rank holds the whole grid (mgx_upload_rows): f[i] holds
+ * the OWNED rows [ra, rb) (mgx_owned_rows) of local part i, (rb-ra)*(N+1)
+ * doubles, reference layout.  All parts or none on an allocation failure.  A
+ * partitioned context with no partitioned level returns MGX_E_ARG (use
+ * mgx_set_source, as mgx_upload_rows asks for mgx_upload); on a single-GPU
+ * context part 0 is all rows and the call is mgx_set_source(ctx, f[0]).
+ *
+ * Profile accounting (kind MGX_K_RHS): the separable pass's compulsory bytes
+ * are 16 per point with velocity factors ("source_sv" 1: u in, rhs out), 32
+ * without (u, v1, v2, rhs), against 24 / 40 of the field pass; its algorithmic
+ * bytes are those of the source-free pass.  Measured on one MI355X (DESIGN.md
+ * section 9, N=16384): 0.95 ms against 1.29 ms for the field pass with
+ * velocity factors, the same for 1, 2 and 4 terms; mgx_step still does not
+ * fuse the right-hand side while any source is set (see above). */
+#define MGX_SOURCE_MAX_TERMS 4
 int mgx_set_source(mgx_ctx *ctx, const double *f);
 int mgx_set_source_device(mgx_ctx *ctx, const double *f);
 int mgx_set_source_scale(mgx_ctx *ctx, double s);
@@ -495,6 +542,21 @@ int mgx_source_info(mgx_ctx *ctx, int *active, double *scale);
 int mgx_compute_rhs_source(double *rhs, const double *u, long n, const double *v1,
                            const double *v2, double k, double nu, double h, const double *f,
                            double c);
+/* a, b: terms x (N+1) doubles each, term-major.  Host / device pointers. */
+int mgx_set_source_separable(mgx_ctx *ctx, int terms, const double *a, const double *b);
+int mgx_set_source_separable_device(mgx_ctx *ctx, int terms, const double *a, const double *b);
+/* f[i]: the OWNED rows [ra, rb) (mgx_owned_rows) of local part i,
+ * (rb-ra)*(N+1) doubles, reference layout.  Host / device pointers. */
+int mgx_set_source_rows(mgx_ctx *ctx, const double *const *f);
+int mgx_set_source_rows_device(mgx_ctx *ctx, const double *const *f);
+/* *kind: 0 none, 1 field (whole-grid or row blocks), 2 separable; *terms: R or 0
+ * (either may be NULL). */
+int mgx_source_kind(mgx_ctx *ctx, int *kind, int *terms);
+/* The raw op with a separable source (device pointers, null stream): a, b hold
+ * terms x (n+1) doubles, term-major. */
+int mgx_compute_rhs_source_separable(double *rhs, const double *u, long n, const double *v1,
+                                     const double *v2, double k, double nu, double h,
+                                     int terms, const double *a, const double *b, double c);
 
 /* ---- Field diagnostics: statistics and strided samples on the device --------
  * A context keeps its fields in HBM; these calls look at one without moving
