@@ -39,6 +39,10 @@ struct Level {
     // from it and u[1] flagged zero), or -1
     int spec = -1;
     int xin = -1;   // finest level: the input buffer of the last cross-cycle pass
+    // finest level: u[i] holds a packed u_pre (xsmooth.hip), which only the
+    // cross pass reads; set on its u_pre buffer alone, so a buffer is packed
+    // only while it is spec, xin or the input of the cycle under way
+    bool packed[3] = {false, false, false};
     int nxt() const { return cur == 0 ? 1 : 0; }   // ping-pong partner of cur
     double *rhs = nullptr, *v1 = nullptr, *v2 = nullptr;
     // finest level: the next time step's rhs (step mode); coarsest level (n <=
@@ -112,6 +116,9 @@ struct mgx_ctx {
     // mg_outer's cycle predicted to be the last: its finest level runs the
     // post-smoothing alone, not the cross pass (no next-cycle pre-smoothing)
     bool post_only = false;
+    // inside mgx_run_cycles: every cycle ends in a cross pass, so a packed
+    // u_pre is never expanded (mg_outer's last cycle would have to: "xpack" 2)
+    bool fixed_cycles = false;
     // the coarsest solve of level cf_level (cf_reps solves) deferred into the
     // prolongation tile pass of the level above (tuning key "coarse_fuse");
     // -1: none pending
@@ -183,6 +190,7 @@ int launch(mgx_ctx *c, int kind, int level, double bytes, F &&f) {
 
 int prof_flush(mgx_ctx *c);
 int materialize(mgx_ctx *c, int l);
+int op_expand(mgx_ctx *c);   // level 0's current buffer in full form (a packed u_pre)
 int read_norm(mgx_ctx *c, double *norm);
 // store_post: see op_cross (false only between cycles of one run_cycles call)
 int op_vcycle(mgx_ctx *c, int l, double *norm = nullptr, bool store_post = true);

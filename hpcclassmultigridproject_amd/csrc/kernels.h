@@ -192,8 +192,17 @@ struct XArgs {
     // count, no norm), phase 2 = the edge launch only, its partials written
     // after the first `partials_done` and the norm taken over both; 0 = both.
     int band = 0, phase = 0, partials_done = 0;
+    // Packed u_pre (xsmooth.hip, tuning key "xpack"): pin = uin holds only the
+    // colour its pre-smoothing did not update last, at half pitch, and the
+    // boundary vectors behind it; pout = upre is written so.  Whole levels
+    // where xpack_supported; never with rhs_next.
+    bool pin = false, pout = false;
 };
 int launch_xsmooth(const XArgs &a, int sweeps, hipStream_t s);
+bool xpack_supported(long n, double dgs);
+// out = the full form of the packed u_pre `packed` (rhs, velocity, n, pitch
+// and c of `a`, the level the pass ran on)
+void launch_xexpand(const XArgs &a, const double *packed, double *out, hipStream_t s);
 // whether launch_xsmooth supports rhs_next on a whole level of size n
 bool xstep_supported(long n);
 // Cross pass: 1 = interior strips run the unguarded march (default), 0 = all guarded.

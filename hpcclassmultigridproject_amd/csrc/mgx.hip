@@ -325,6 +325,7 @@ int op_smooth(mgx_ctx *c, int l, int sweeps, bool prolong, bool restrict_, bool 
             }
             if (blocks < 0) return fail(MGX_E_ARG, "launch_smooth: unsupported sweeps/mode");
             L.cur = L.nxt();
+            L.packed[L.cur] = false;   // (whole rows written)
             L.zero = false;
             if (rs) c->lv[l + 1].zero = true;
             if (nm && fused_norm) *fused_norm = true;
@@ -503,26 +504,27 @@ static bool cross_ok(mgx_ctx *c) {
 
 // The speculative next-cycle state is only valid while nothing but V-cycles
 // touches the levels; every other mutating entry point drops it.
+// (a packed u_pre is reachable through spec and xin only: it goes with them)
 void drop_spec(mgx_ctx *c) {
-    if (!c->lv.empty()) c->lv[0].spec = -1;
+    if (!c->lv.empty()) {
+        Level &L = c->lv[0];
+        L.spec = -1;
+        if (L.xin >= 0 && L.packed[L.xin]) L.xin = -1;
+        if (!L.packed[L.cur]) L.packed[0] = L.packed[1] = L.packed[2] = false;
+    }
     c->step_spec = false;
 }
 
-// k_xsmooth on level 0: u_post (cycle k, returned by mg_outer if it stops
-// here) into one free buffer, u_pre (cycle k+1's pre-smoothing) into the
-// other, the residual of u_post -> c->dscal[0], the restriction of u_pre's
-// residual -> rhs[1] (u[1] flagged zero for cycle k+1).
-static int op_cross(mgx_ctx *c, bool store_post, bool rs = false) {
+// tuning key "xpack": 0 whole rows, 1 packed, 2 (default) packed in fp_mode
+// fma inside mgx_run_cycles only -- measured: level 0 -4.8 % there, +5 % in
+// the bitwise mode, whose rebuilt colour costs a division per point; and
+// mg_outer's last cycle reads whole rows, so there a packed u_pre costs an
+// expansion pass per call, more than a few cycles' gain
+long g_xpack = 2;
+
+static mgx::XArgs cross_args(mgx_ctx *c) {
     Level &L = c->lv[0], &Cl = c->lv[1];
-    CHK(materialize(c, 1));
-    if (rs && !L.rhs_alt) return fail(MGX_E_INTERNAL, "step-mode cross pass without rhs_alt");
-    int P = -1, Q = -1;
-    for (int i = 0; i < 3; ++i)
-        if (i != L.cur) (P < 0 ? P : Q) = i;
     mgx::XArgs A;
-    A.uin = L.U();
-    A.upost = L.u[P];
-    A.upre = L.u[Q];
     A.rhs = L.rhs;
     A.v1 = L.v1;
     A.v2 = L.v2;
@@ -534,11 +536,57 @@ static int op_cross(mgx_ctx *c, bool store_post, bool rs = false) {
     A.n = L.n;
     A.pitch = L.pitch;
     A.c = L.coef;
-    A.store_post = store_post;
     A.sa1 = L.sa1;
     A.sb1 = L.sb1;
     A.sa2 = L.sa2;
     A.sb2 = L.sb2;
+    return A;
+}
+
+// Level 0's current buffer in full form, for the passes that read whole rows:
+// a packed u_pre is expanded into the ping-pong partner (free wherever this
+// is called: the cycle's other two buffers hold a dead u_post and a dead or
+// dropped u_pre), which becomes the current buffer.
+int op_expand(mgx_ctx *c) {
+    Level &L = c->lv[0];
+    if (!L.packed[L.cur]) return MGX_OK;
+    const int src = L.cur, dst = L.nxt();
+    const mgx::XArgs A = cross_args(c);
+    // the packed rows, rhs (+ v1, v2) read; the full rows written
+    const double cbytes = 8.0 * (2.5 * L.M() + (L.sa1 ? 0.0 : 2.0 * L.M()));
+    // (profiled as what it is: half a sweep, 40 B per point a sweep)
+    CHK(launch(c, MGX_K_GS, 0, 20.0 * L.M(), cbytes,
+               [&] { mgx::launch_xexpand(A, L.u[src], L.u[dst], c->stream); }));
+    L.packed[src] = L.packed[dst] = false;
+    if (L.xin == src) L.xin = dst;
+    L.cur = dst;
+    return MGX_OK;
+}
+
+// k_xsmooth on level 0: u_post (cycle k, returned by mg_outer if it stops
+// here) into one free buffer, u_pre (cycle k+1's pre-smoothing) into the
+// other, the residual of u_post -> c->dscal[0], the restriction of u_pre's
+// residual -> rhs[1] (u[1] flagged zero for cycle k+1).
+static int op_cross(mgx_ctx *c, bool store_post, bool rs = false) {
+    Level &L = c->lv[0], &Cl = c->lv[1];
+    CHK(materialize(c, 1));
+    if (rs && !L.rhs_alt) return fail(MGX_E_INTERNAL, "step-mode cross pass without rhs_alt");
+    // u_pre goes out packed (tuning key "xpack") wherever the pass has that
+    // form; step mode and the tile form read and write whole rows
+    const bool pk_ok = !rs && mgx::xpack_supported(L.n, L.coef.dgs);
+    const bool pout = pk_ok && (g_xpack == 1 || (g_xpack == 2 && L.coef.fm && c->fixed_cycles));
+    if (!pout) CHK(op_expand(c));   // (a packed input comes with a packed output only)
+    const bool pin = L.packed[L.cur];
+    int P = -1, Q = -1;
+    for (int i = 0; i < 3; ++i)
+        if (i != L.cur) (P < 0 ? P : Q) = i;
+    mgx::XArgs A = cross_args(c);
+    A.uin = L.U();
+    A.upost = L.u[P];
+    A.upre = L.u[Q];
+    A.store_post = store_post;
+    A.pin = pin;
+    A.pout = pout;
     if (rs) {
         A.rhs_next = L.rhs_alt;
         A.norm2_out = c->dscal + 6;
@@ -554,8 +602,10 @@ static int op_cross(mgx_ctx *c, bool store_post, bool rs = false) {
     // step, and its rhs written)
     // (with velocity factors v1 / v2 are not read: two fine arrays fewer)
     const double bytes_rs = rs ? (32.0 + 48.0) * L.M() : 0.0;
+    // (a packed u_pre: half a fine array per packed side)
     const double cbytes = 8.0 * ((store_post ? 6.0 : 5.0) * L.M() - (L.sa1 ? 2.0 * L.M() : 0.0) +
-                                 2.0 * Cl.M() + (rs ? L.M() : 0.0));
+                                 2.0 * Cl.M() + (rs ? L.M() : 0.0) -
+                                 0.5 * L.M() * ((pin ? 1 : 0) + (pout ? 1 : 0)));
     int blocks = 0;
     CHK(launch(c, MGX_K_XSMOOTH, 0, bytes + bytes_rs, cbytes,
                [&] { blocks = mgx::launch_xsmooth(A, k, c->stream); }));
@@ -563,6 +613,8 @@ static int op_cross(mgx_ctx *c, bool store_post, bool rs = false) {
     L.xin = L.cur;
     L.cur = P;
     L.spec = Q;
+    L.packed[P] = false;
+    L.packed[Q] = pout;
     L.zero = false;
     Cl.zero = true;
     return MGX_OK;
@@ -701,6 +753,7 @@ int op_vcycle(mgx_ctx *c, int l, double *norm, bool store_post) {
         }
         if (c->post_only) {   // the last cycle: prolongation + post-smoothing + norm only
             bool fused = false;
+            CHK(op_expand(c));   // (k_wsmooth reads whole rows)
             CHK(op_smooth(c, 0, c->opt.nsmooth, /*prolong=*/true, false, /*norm=*/true, &fused));
             L.spec = -1;
             return fused ? read_norm(c, norm) : op_residual_norm(c, 0, norm);
@@ -867,6 +920,7 @@ static int op_rhs_norm_pre(mgx_ctx *c, double *res0) {
     }));
     if (blocks < 0) return fail(MGX_E_ARG, "launch_smooth: rhs+norm+pre-smoothing unsupported");
     L.spec = out;   // the first cycle's pre-smoothed u (op_vcycle takes it)
+    L.packed[out] = false;
     L.zero = false;
     Cl.zero = true;
     return read_norm(c, res0);
@@ -896,6 +950,7 @@ static int op_redo_post(mgx_ctx *c) {
     L.cur = L.xin;
     L.spec = -1;
     L.zero = false;
+    CHK(op_expand(c));   // (the pass's input was a packed u_pre: k_wsmooth reads whole rows)
     c->lv[1].zero = false;   // u[1] still holds the correction the pass prolonged
     return op_smooth(c, 0, c->opt.nsmooth, /*prolong=*/true, false, false, nullptr);
 }
@@ -1367,6 +1422,7 @@ int mgxi::upload_ctx(mgx_ctx *c, const double *u0, const double *v1, const doubl
     L.zero = false;
     L.spec = -1;
     L.xin = -1;
+    L.packed[0] = L.packed[1] = L.packed[2] = false;
     c->step_spec = false;   // a pending next-step state belongs to the old fields
     const double *src[3] = {u0, v1, v2};
     double *dst[3] = {L.u[0], L.v1, L.v2};
@@ -1397,6 +1453,7 @@ static int set_velocity_impl(mgx_ctx *c, const double *v1, const double *v2,
     // deferred coarsest solve: all formed with the old velocity
     L.spec = -1;
     L.xin = -1;
+    L.packed[0] = L.packed[1] = L.packed[2] = false;
     c->step_spec = false;
     c->step_next = false;
     c->step_res0 = 0;
@@ -1644,6 +1701,7 @@ static int download_impl(mgx_ctx *c, int level, int field, double *out, hipMemcp
         return fail(MGX_E_ARG, "mgx_download: bad args");
     HIPCHK(hipSetDevice(c->device));
     CHK(materialize(c, level));
+    if (level == 0 && field == 0) CHK(op_expand(c));   // (a cycle that failed half-way)
     Level &L = c->lv[level];
     const double *src = field == 0 ? L.U() : field == 1 ? L.rhs : field == 2 ? L.v1 : L.v2;
     const size_t row = (L.n + 1) * sizeof(double);
@@ -1992,7 +2050,12 @@ int mgx_run_cycles(mgx_ctx *c, int cycles, double *res) {
     if (!c || cycles < 0) return fail(MGX_E_ARG, "mgx_run_cycles: bad args");
     drop_step_spec(c);
     double r = 0;
-    for (int k = 0; k < cycles; ++k) CHK(cycle_norm(c, &r, /*store_post=*/k == cycles - 1));
+    c->fixed_cycles = true;
+    int rc = MGX_OK;
+    for (int k = 0; k < cycles && rc == MGX_OK; ++k)
+        rc = cycle_norm(c, &r, /*store_post=*/k == cycles - 1);
+    c->fixed_cycles = false;
+    CHK(rc);
     if (res) *res = r;
     return MGX_OK;
 }
@@ -2316,6 +2379,11 @@ extern "C" int mgx_set_tuning(const char *key, long value) {
         mgx::set_xfast(value);
         return MGX_OK;
     }
+    if (!strcmp(key, "xpack")) {
+        if (value < 0 || value > 2) return fail(MGX_E_ARG, "xpack must be 0, 1 or 2");
+        mgxi::g_xpack = value;
+        return MGX_OK;
+    }
     if (!strcmp(key, "tile32_min_n")) {
         if (value < 0) return fail(MGX_E_ARG, "tile32_min_n must be >= 0");
         mgx::set_tile32_min_n(value);
@@ -2444,6 +2512,10 @@ extern "C" int mgx_get_tuning(const char *key, long *value) {
     }
     if (!strcmp(key, "dist_min_rows")) {
         *value = mgxi::g_dist_min_rows;
+        return MGX_OK;
+    }
+    if (!strcmp(key, "xpack")) {
+        *value = mgxi::g_xpack;
         return MGX_OK;
     }
     if (!strcmp(key, "xfast")) {

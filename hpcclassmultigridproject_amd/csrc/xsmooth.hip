@@ -99,8 +99,39 @@ struct XCfg {
 // contracted update (one fma each), every update is four fmas and every
 // residual d*(update - u).  B's time-step rhs (RS) keeps the reference
 // expressions (gs.cpp:44, stored unscaled) and is scaled after.
-template <int WPB, int K, bool G, bool RS = false, bool SV = false, bool FM = false>
-__global__ __launch_bounds__(128 * WPB) void k_xsmooth(
+//
+// PI / PO (packed u_pre, tuning key "xpack"): the pre-smoothing's last stage
+// (h = S-1, odd) updates the points with (row + column) odd from the other
+// colour's final values, the row's rhs and the row's coefficients -- all of
+// which the next pass holds anyway.  So B stores only the colour it does not
+// update last (PO: row R at half pitch, packed column j = the point (R, 2j +
+// (R & 1)), 8 B per lane) and A of the next pass (PI) rebuilds the other one
+// with B's expression on the same operands -- the same bits -- before it adds
+// the prolongation: half a fine array less written, half less read.  The
+// Dirichlet points of the dropped colour cannot be rebuilt: the guarded
+// kernel, which owns the whole boundary, carries the four boundary vectors
+// behind the packed rows (XSide), from its input's boundary (full input) or
+// its input's vectors (packed input).
+struct XSide {   // offsets (doubles) from the packed buffer's base
+    long top, bot, left, right;
+    __host__ __device__ XSide(int n, long pitch) {
+        top = (long)(n + 1) * (pitch >> 1);
+        bot = top + pitch;
+        left = bot + pitch;
+        right = left + n + 2;
+    }
+};
+__device__ __forceinline__ void st1s_ifu(double *row, int col, bool on, double v) {
+    double *p = reinterpret_cast<double *>(const_cast<char *>(rowb(row, (unsigned)col * 8u)));
+#if MGX_NTST
+    if (on) __builtin_nontemporal_store(v, p);
+#else
+    if (on) *p = v;
+#endif
+}
+
+template <int WPB, int K, bool G, bool RS, bool SV, bool FM, bool PI, bool PO>
+__device__ __forceinline__ void xsmooth_body(
     const double *__restrict__ uin, double *__restrict__ upost, double *__restrict__ upre,
     const double *__restrict__ rhs, const double *__restrict__ v1, const double *__restrict__ v2,
     const double *__restrict__ uc, long pitchc, double *__restrict__ rhsc,
@@ -119,8 +150,14 @@ __global__ __launch_bounds__(128 * WPB) void k_xsmooth(
     // u 3-4 steps or rhs/v 5 measured no better (N=16384, tools/ab_libs.sh).
     // (the fma interior kernel on the velocity factors: 5 steps, -0.8 % on
     // level 0 in three alternated rounds, 2 VGPRs spilled; XU 3 no change)
-    constexpr int XRV = (FM && SV && !G && !RS) ? MGX_XRV + 1 : MGX_XRV;
-    constexpr int XU = MGX_XU;
+    // (a packed input: the row's rhs / factors are first used three steps
+    // earlier, where the row is unpacked, so the unguarded kernels on the
+    // velocity factors load them the one step further ahead the ring allows
+    // -- with v1 / v2 rows in flight too that spills 46-62 VGPRs; the guarded
+    // ones hold one u row less in flight instead, which keeps them, with the
+    // packed rows' ring, within two waves per SIMD)
+    constexpr int XRV = ((FM && !RS) || PI) && SV && !G ? MGX_XRV + 1 : MGX_XRV;
+    constexpr int XU = (PI && G && MGX_XU > 1) ? MGX_XU - 1 : MGX_XU;
     // A forms each row's coefficients once (MGX_XACOEF; B always does).  Not
     // in the guarded edge kernel: there it takes the kernel past 256 VGPRs
     // (one wave per SIMD), and the edge launch is latency bound
@@ -129,6 +166,9 @@ __global__ __launch_bounds__(128 * WPB) void k_xsmooth(
     // row s+XRV takes the ring slot of row s+XRV-NR, last used by A's norm of
     // row s+1-S
     static_assert(XRV >= 2 && XRV <= NR - S + 1, "rhs/v prefetch distance");
+    // (a packed row is rebuilt from its rhs / factors two steps before its first stage)
+    static_assert(!PI || XRV >= 4, "rhs/v prefetch distance of a packed input");
+    static_assert(!(RS && (PI || PO)), "step mode runs on the full format");
     __shared__ double2 uring[WPB][NU][64];
     // rhs / t1 / t2 planes: each hand-off access is 16 B per lane, unit stride
     __shared__ double2 rdring[WPB][NRD][3][64];
@@ -145,7 +185,9 @@ __global__ __launch_bounds__(128 * WPB) void k_xsmooth(
     // row offsets as 32 x 32 -> 64-bit products (the pitches are < 2^31
     // elements): two scalar multiplies per row address instead of a 64-bit one
     const int ip = (int)pitch, ipc = (int)pitchc;
+    const int ihp = ip >> 1;   // pitch of a packed row
     auto rowoff = [](int r, int p) { return (long)r * (long)p; };
+    const XSide sd(n, pitch);
 
     // One march of the pair over owned rows [a, b) of the strip whose lane 0
     // is column cb, owning columns [k0, k1) (G: see above; the unguarded form
@@ -184,7 +226,7 @@ __global__ __launch_bounds__(128 * WPB) void k_xsmooth(
         // an even row needs only the coarse row below it)
         auto load_u = [&](int R, UPre &u, const bool odd) {
             const int Rc = min(max(R, lo), hi);
-            u.X = ld2u(uin + rowoff(Rc, ip), bcl);
+            if (!PI) u.X = ld2u(uin + rowoff(Rc, ip), bcl);   // (PI: load_pk, a row further ahead)
             const double *p0 = uc + rowoff(Rc >> 1, ipc);
             u.q00 = ld1u(p0, bjl);
             u.q01 = ld1u(p0, bjl1);
@@ -194,9 +236,28 @@ __global__ __launch_bounds__(128 * WPB) void k_xsmooth(
                 u.q11 = ld1u(p1, bjl1);
             }
         };
+        // PI: packed u rows in flight and in use, a ring by row.  .x: the row's
+        // kept colour (column c0 + (R & 1)); .y (guarded): the Dirichlet value
+        // of its dropped column, where that is one (a clamped row's values
+        // are never used: any in-bounds word)
+        double2 pk[NR];
+#pragma unroll
+        for (int i = 0; i < NR; ++i) pk[i] = make_double2(0.0, 0.0);
+        auto load_pk = [&](int R, double2 &k, const bool odd) {
+            const int Rc = min(max(R, lo), hi);
+            k.x = ld1u(uin + rowoff(Rc, ihp), bjl);
+            if (G) {
+                if (odd) {   // dropped column c0: the side columns
+                    if (c0 == 0 || c0 == n) k.y = uin[(c0 == 0 ? sd.left : sd.right) + Rc];
+                } else if (Rc == 0 || Rc == n) {   // dropped column c0 + 1
+                    k.y = ld1u(uin + (Rc == 0 ? sd.top : sd.bot), bcl + 8u);
+                }
+            }
+        };
         // + prolongation (gs.cpp:238-265); static parity, select (see k_wsmooth)
-        auto make_u = [&](int R, const UPre &u, const bool odd) {
-            double2 v = u.X;
+        // (X: the row before the prolongation, u.X or its unpacked form)
+        auto make_ux = [&](int R, const double2 X, const UPre &u, const bool odd) {
+            double2 v = X;
             double2 pv;
             const double q01 = (!GM || j1) ? u.q01 : 0.0;
             const double q11 = (!GM || j1) ? u.q11 : 0.0;
@@ -212,6 +273,7 @@ __global__ __launch_bounds__(128 * WPB) void k_xsmooth(
             v.y = on ? v.y + pv.y : v.y;
             return v;
         };
+        auto make_u = [&](int R, const UPre &u, const bool odd) { return make_ux(R, u.X, u, odd); };
         // SV: the lane's column factors scaled by h/2 (exact), and a ring of
         // row factors (wave-uniform: SGPRs), slot q = the rd slot of the row
         double2 bh1 = make_double2(0.0, 0.0), bh2 = bh1;
@@ -298,7 +360,9 @@ __global__ __launch_bounds__(128 * WPB) void k_xsmooth(
         // A's first step (aligned to NR so ring indices and parities are
         // static); B runs D steps behind; the last iteration is B's last step
         // (rounded up to whole pairs: an extra step stores nothing)
-        int s0 = a - EB - EA - (RS ? 1 : 0);
+        // (PI: the rebuilt colour is one more stage in front, and the first two
+        // rows enter without it)
+        int s0 = a - EB - EA - (RS ? 1 : 0) - (PI ? 2 : 0);
         s0 = s0 >= 0 ? (s0 / NR) * NR : -(((-s0) + NR - 1) / NR) * NR;
         s0 = __builtin_amdgcn_readfirstlane(s0);
         const int iters = ((b + EB - 3) + D - s0 + 1 + 1) & ~1;
@@ -317,7 +381,7 @@ __global__ __launch_bounds__(128 * WPB) void k_xsmooth(
             const double2 z = make_double2(0.0, 0.0);
             cf[i] = CoefRow{z, z, z, z};
         }
-        auto to_coef = [&](const RowData &d, CoefRow &k) {
+        auto to_coef_c = [&](const RowData &d, CoefRow &k, const Coef &c) {
             if (FM) {
                 k.cn = make_double2(fm_mp(d.x.x, c), fm_mp(d.x.y, c));
                 k.cw = make_double2(fm_mp(d.y.x, c), fm_mp(d.y.y, c));
@@ -330,6 +394,7 @@ __global__ __launch_bounds__(128 * WPB) void k_xsmooth(
             k.cs = make_double2(c.rr * (d.x.x + c.nu), c.rr * (d.x.y + c.nu));
             k.ce = make_double2(c.rr * (d.y.x + c.nu), c.rr * (d.y.y + c.nu));
         };
+        auto to_coef = [&](const RowData &d, CoefRow &k) { to_coef_c(d, k, c); };
         // stage h at ring phase q on row r (as `stage`), from the coefficients
         auto stage_c = [&](const int q, const int h, const int r) {
             const int iR = (q + 1 - h + 2 * NR) % NR;
@@ -367,6 +432,47 @@ __global__ __launch_bounds__(128 * WPB) void k_xsmooth(
             return rd[iR].r.x - (c.dgs * ur[iR].x + k.cn.x * ur[iN].x + k.cw.x * uW +
                                  k.cs.x * ur[iS].x + k.ce.x * ur[iR].y);
         };
+        // PI: row R (ring slot q, raw rhs / factors of the row already there)
+        // in full form before the prolongation: its kept colour as loaded, the
+        // other one rebuilt as the last stage of the pass that packed it formed
+        // it (stage_c's expressions on the kept colour of rows R-1, R, R+1).
+        // The row's f', t and coefficients are formed again at its ordinary
+        // first stage, steps later, from fresh copies of the scalars: shared
+        // values would stay live for those steps (registers the march lacks).
+        auto unpack = [&](const int R, const int q, const bool odd) {
+            const double kR = pk[q].x, kN = pk[(q + NR - 1) % NR].x, kS = pk[(q + 1) % NR].x;
+            Coef cu = c;
+            asm volatile("" : "+s"(cu.rdgs), "+s"(cu.g), "+s"(cu.nu));
+            RowData d = rd[q];
+            if (SV) {
+                double a1 = ar1[q], a2 = ar2[q];
+                asm volatile("" : "+v"(a1), "+v"(a2));
+                d.x = make_double2(a1 * bh1.x, a1 * bh1.y);
+                d.y = make_double2(a2 * bh2.x, a2 * bh2.y);
+            }
+            if (FM) d.r = make_double2(d.r.x * cu.rdgs, d.r.y * cu.rdgs);
+            CoefRow k;
+            to_coef_c(d, k, cu);
+            const bool rin = !G || (R >= 1 && R <= n - 1);
+            if (!odd) {   // column c0 + 1 from W = c0 (own), E = c0 + 2 (next lane)
+                const double uE = dpp_shl1(kR);
+                const double v = FM ? fm_upd(d.r.y, k.cn.y, kN, k.cw.y, kR, k.cs.y, kS, k.ce.y, uE)
+                                    : div_diag<!G>(d.r.y - k.cn.y * kN - k.cw.y * kR -
+                                                       k.cs.y * kS - k.ce.y * uE,
+                                                   cu);
+                if (!G) return make_double2(kR, v);
+                const bool edge = act && c0 + 1 <= n && (R == 0 || R == n);
+                return make_double2(kR, (rin && in1) ? v : edge ? pk[q].y : 0.0);
+            }
+            const double uW = dpp_shr1(kR);   // column c0 from W = c0 - 1, E = c0 + 1 (own)
+            const double v = FM ? fm_upd(d.r.x, k.cn.x, kN, k.cw.x, uW, k.cs.x, kS, k.ce.x, kR)
+                                : div_diag<!G>(d.r.x - k.cn.x * kN - k.cw.x * uW - k.cs.x * kS -
+                                                   k.ce.x * kR,
+                                               cu);
+            if (!G) return make_double2(v, kR);
+            const bool edge = act && (c0 == 0 || c0 == n) && R >= 0 && R <= n;
+            return make_double2((rin && in0) ? v : edge ? pk[q].y : 0.0, kR);
+        };
         // one loop per role (a role branch inside the step would make the
         // waitcnt pass see A's pending loads on B's path and drain them)
         int it = 0;
@@ -374,17 +480,34 @@ __global__ __launch_bounds__(128 * WPB) void k_xsmooth(
 #pragma unroll
             for (int d = 0; d < 3; ++d) {
                 load_u(s0 + d, up[d], d & 1);
-                ur[d] = make_u(s0 + d, up[d], d & 1);
+                if (!PI) ur[d] = make_u(s0 + d, up[d], d & 1);
             }
 #pragma unroll
             for (int d = 3; d < 3 + XU; ++d) load_u(s0 + d, up[d], d & 1);
 #pragma unroll
             for (int d = 1; d < XRV; ++d) load_rv(s0 + d, d);
+            if (PI) {
+                // rows s0, s0+1 are outside every cone: no rebuild; row s+3 is
+                // unpacked at step s (off the stages' dependency chain), with
+                // row s+4 there and rows up to s+4+XU in flight
+#pragma unroll
+                for (int d = 0; d < 4 + XU; ++d) load_pk(s0 + d, pk[d], d & 1);
+#pragma unroll
+                for (int d = 0; d < 2; ++d)
+                    ur[d] = make_ux(s0 + d, make_double2(pk[d].x, pk[d].x), up[d], d & 1);
+                ur[2] = make_ux(s0 + 2, unpack(s0 + 2, 2, false), up[2], false);
+            }
             for (;;) {
 #pragma unroll
                 for (int p = 0; p < NR; ++p) {   // s == p (mod NR)
                     const int s = s0 + it + (p & 1);
-                    ur[(p + 3) % NR] = make_u(s + 3, up[(p + 3) % NR], (p + 3) & 1);
+                    if (PI) {
+                        ur[(p + 3) % NR] = make_ux(s + 3, unpack(s + 3, (p + 3) % NR, (p + 3) & 1),
+                                                   up[(p + 3) % NR], (p + 3) & 1);
+                        load_pk(s + 4 + XU, pk[(p + 4 + XU) % NR], (p + 4 + XU) & 1);
+                    } else {
+                        ur[(p + 3) % NR] = make_u(s + 3, up[(p + 3) % NR], (p + 3) & 1);
+                    }
                     load_u(s + 3 + XU, up[(p + 3 + XU) % NR], (p + 3 + XU) & 1);   // XU ahead
                     first_use((p + 1) % NR);   // row s+1: first used by stage 0 below
                     if (XACOEF) {
@@ -517,8 +640,20 @@ __global__ __launch_bounds__(128 * WPB) void k_xsmooth(
                     for (int h = 0; h < S; ++h) stage_c(q, h, s + 1 - h);
                     {
                         const int ro = s + 2 - S;
-                        st2_ifu(upre + rowoff(ro, ip), c0, own(ro),
-                                ur[(q + 2 - S + 2 * NR) % NR]);
+                        const double2 uf = ur[(q + 2 - S + 2 * NR) % NR];
+                        if (PO) {
+                            // the colour the last stage left alone: column c0 of
+                            // an even row, c0 + 1 of an odd one (static parity)
+                            const bool od = ((q + 2 - S) & 1) != 0;
+                            st1s_ifu(upre + rowoff(ro, ihp), c0 >> 1, own(ro), od ? uf.y : uf.x);
+                            if (G && own(ro)) {   // the Dirichlet values beside it
+                                if (ro == 0 || ro == n) st2(upre + (ro == 0 ? sd.top : sd.bot) + c0, uf);
+                                if (od && (c0 == 0 || c0 == n))
+                                    upre[(c0 == 0 ? sd.left : sd.right) + ro] = uf.x;
+                            }
+                        } else {
+                            st2_ifu(upre + rowoff(ro, ip), c0, own(ro), uf);
+                        }
                     }
                     if (((q + 1 - S) & 1) == 0) {   // compile-time row parity
                         // residual -> coarse rhs at the even-even points (:73-75)
@@ -558,6 +693,90 @@ __global__ __launch_bounds__(128 * WPB) void k_xsmooth(
         const double tot2 = wave_sum(acc2);   // B only (A's are +0)
         if (l == 0) partials2[(long)blockIdx.x * 2 * WPB + wv] = tot2;
     }
+}
+
+#define MGX_XSMOOTH_PARAMS                                                                         \
+    const double *__restrict__ uin, double *__restrict__ upost, double *__restrict__ upre,        \
+        const double *__restrict__ rhs, const double *__restrict__ v1,                             \
+        const double *__restrict__ v2, const double *__restrict__ uc, long pitchc,                 \
+        double *__restrict__ rhsc, double *__restrict__ partials, int n, long pitch,               \
+        MarchRegions reg, long units_per_wg, Coef c, int lo, int hi, int store_post,               \
+        double *__restrict__ rhs_next, double *__restrict__ partials2,                             \
+        const double *__restrict__ sa1, const double *__restrict__ sb1,                            \
+        const double *__restrict__ sa2, const double *__restrict__ sb2
+#define MGX_XSMOOTH_ARGS                                                                           \
+    uin, upost, upre, rhs, v1, v2, uc, pitchc, rhsc, partials, n, pitch, reg, units_per_wg, c, lo, \
+        hi, store_post, rhs_next, partials2, sa1, sb1, sa2, sb2
+
+// the full format on both sides
+template <int WPB, int K, bool G, bool RS = false, bool SV = false, bool FM = false>
+__global__ __launch_bounds__(128 * WPB) void k_xsmooth(MGX_XSMOOTH_PARAMS) {
+    xsmooth_body<WPB, K, G, RS, SV, FM, false, false>(MGX_XSMOOTH_ARGS);
+}
+// full u in, packed u_pre out (the first cross pass after a plain pre-smoothing)
+template <int WPB, int K, bool G, bool SV, bool FM>
+__global__ __launch_bounds__(128 * WPB) void k_xsmooth_fp(MGX_XSMOOTH_PARAMS) {
+    xsmooth_body<WPB, K, G, false, SV, FM, false, true>(MGX_XSMOOTH_ARGS);
+}
+// packed on both sides (every later one)
+template <int WPB, int K, bool G, bool SV, bool FM>
+__global__ __launch_bounds__(128 * WPB) void k_xsmooth_pp(MGX_XSMOOTH_PARAMS) {
+    xsmooth_body<WPB, K, G, false, SV, FM, true, true>(MGX_XSMOOTH_ARGS);
+}
+// format: 0 full -> full, 1 full -> packed, 2 packed -> packed
+template <int WPB, int K, bool G, bool RS, bool SV, bool FM, int PK>
+static constexpr auto xsmooth_kernel() {
+    if constexpr (PK == 0)
+        return &k_xsmooth<WPB, K, G, RS, SV, FM>;
+    else if constexpr (PK == 1)
+        return &k_xsmooth_fp<WPB, K, G, SV, FM>;
+    else
+        return &k_xsmooth_pp<WPB, K, G, SV, FM>;
+}
+
+// A packed u_pre in full form (the passes that read whole rows: the plain
+// post-smoothing of mg_outer's last cycle, the recomputed u_post, the
+// step-mode pass): one thread per column pair, the dropped colour by the
+// expressions of the march's stage_c / unpack, its Dirichlet points from the
+// side vectors.
+template <bool SV, bool FM>
+__global__ __launch_bounds__(256) void k_xexpand(
+    const double *__restrict__ pk, double *__restrict__ out, const double *__restrict__ rhs,
+    const double *__restrict__ v1, const double *__restrict__ v2, const double *__restrict__ sa1,
+    const double *__restrict__ sb1, const double *__restrict__ sa2,
+    const double *__restrict__ sb2, int n, long pitch, Coef c) {
+    const int nbx = (n / 2 + 256) / 256;   // workgroups per row
+    const int j = (int)(blockIdx.x % nbx) * 256 + threadIdx.x, R = blockIdx.x / nbx;
+    const int c0 = 2 * j;
+    if (c0 > n) return;
+    const long hp = pitch >> 1;
+    const XSide sd(n, pitch);
+    const bool odd = R & 1;
+    const int cd = odd ? c0 : c0 + 1;   // the dropped column
+    const double kR = pk[R * hp + j];
+    double dv = 0.0;
+    if (R >= 1 && R <= n - 1 && cd >= 1 && cd <= n - 1) {
+        const double kN = pk[(R - 1) * hp + j], kS = pk[(R + 1) * hp + j];
+        const double kO = pk[R * hp + (odd ? j - 1 : j + 1)];
+        const double uW = odd ? kO : kR, uE = odd ? kR : kO;
+        const long o = (long)R * pitch + cd;
+        const double hh = c.h * 0.5;
+        const double f = rhs[o];
+        const double t1 = SV ? sa1[R] * (sb1[cd] * hh) : v1[o] * hh;
+        const double t2 = SV ? sa2[R] * (sb2[cd] * hh) : v2[o] * hh;
+        if (FM) {
+            const double mn = fm_mp(t1, c), mw = fm_mp(t2, c);
+            dv = fm_upd(f * c.rdgs, mn, kN, mw, uW, fm_ms(mn, c), kS, fm_ms(mw, c), uE);
+        } else {
+            const double cn = c.rr * (c.nu - t1), cw = c.rr * (c.nu - t2);
+            const double cs = c.rr * (t1 + c.nu), ce = c.rr * (t2 + c.nu);
+            dv = div_diag(f - cn * kN - cw * uW - cs * kS - ce * uE, c);
+        }
+    } else if (cd <= n) {
+        dv = R == 0 ? pk[sd.top + cd]
+                    : R == n ? pk[sd.bot + cd] : pk[(cd == 0 ? sd.left : sd.right) + R];
+    }
+    st2(out + (long)R * pitch + c0, odd ? make_double2(dv, kR) : make_double2(kR, dv));
 }
 
 // k_xtile: the cross-cycle pass of k_xsmooth as 2-D LDS tiles, for the edge
@@ -807,6 +1026,34 @@ long g_xfast = 1;   // unguarded interior march kernels (tuning key "xfast")
 void set_xfast(long v) { g_xfast = v; }
 long get_xfast() { return g_xfast; }
 
+// Whether the cross pass of a whole level of size n runs in a form that has
+// the packed u_pre: the two march launches or the guarded one, not the LDS
+// tiles of short levels (k_xtile reads and writes whole rows).
+extern long g_xtile_max_rows;
+bool xpack_supported(long n, double dgs) {
+    const bool split = g_xfast != 0 && dgs > 0;
+    return n >= 64 && !(n & 1) && !(split && n + 1 <= g_xtile_max_rows);
+}
+
+void launch_xexpand(const XArgs &A, const double *packed, double *out, hipStream_t s) {
+    const bool sv = A.sa1 && A.sb1 && A.sa2 && A.sb2;
+    const dim3 grid((unsigned)((A.n / 2 + 256) / 256 * (A.n + 1))), block(256);
+#define MGX_XEXPAND(SV, FM)                                                                     \
+    MGX_LAUNCH((k_xexpand<SV, FM>), grid, block, s, packed, out, A.rhs, A.v1, A.v2, A.sa1, A.sb1, \
+               A.sa2, A.sb2, (int)A.n, A.pitch, A.c)
+    if (A.c.fm) {
+        if (sv)
+            MGX_XEXPAND(true, true);
+        else
+            MGX_XEXPAND(false, true);
+    } else if (sv) {
+        MGX_XEXPAND(true, false);
+    } else {
+        MGX_XEXPAND(false, false);
+    }
+#undef MGX_XEXPAND
+}
+
 template <int WPB, int K, bool G, bool RS, bool SV, bool FM>
 static int xsmooth_slots() {
     static int slots = 0;   // resident workgroups of this instantiation
@@ -825,23 +1072,40 @@ static int xsmooth_slots() {
 // One launch over `reg`; min_rows: the fewest rows per workgroup (each
 // workgroup's march pays a warm-up of ~EA + EB + D rows).  Returns the norm
 // partials written (grid * 2 * WPB: one per wave) at `partials`.
-template <int WPB, int K, bool G, bool RS, bool SV, bool FM>
-static int xsmooth_launch_sv(const XArgs &A, const MarchRegions &reg, double *partials, int lo,
+template <int WPB, int K, bool G, bool RS, bool SV, bool FM, int PK>
+static int xsmooth_launch_pk(const XArgs &A, const MarchRegions &reg, double *partials, int lo,
                              int hi, long min_rows, long max_wgs, hipStream_t s) {
     const long total = reg.pre[reg.count];
     if (total <= 0) return 0;
     long upw;
     MarchRegions r;
     using X = XCfg<K>;
+    // (the full-format kernel's slots for every format: one work split, so the
+    // norm partials add up in one order whatever the format)
     const unsigned grid = plan_march(reg, WPB, xsmooth_slots<WPB, K, G, RS, SV, FM>(), min_rows,
                                      max_wgs, X::EA + X::EB + X::D + X::NR / 2, upw, r);
     // RS: the second partials (the next step's initial norm) at the same
     // offsets, kNormBlocks further on
-    MGX_LAUNCH((k_xsmooth<WPB, K, G, RS, SV, FM>), dim3(grid), dim3(128 * WPB), s, A.uin,
-               A.upost, A.upre, A.rhs, A.v1, A.v2, A.uc, A.pitchc, A.rhsc, partials, (int)A.n,
-               A.pitch, r, upw, A.c, lo, hi, A.store_post ? 1 : 0, A.rhs_next,
+    MGX_LAUNCH((xsmooth_kernel<WPB, K, G, RS, SV, FM, PK>()), dim3(grid), dim3(128 * WPB), s,
+               A.uin, A.upost, A.upre, A.rhs, A.v1, A.v2, A.uc, A.pitchc, A.rhsc, partials,
+               (int)A.n, A.pitch, r, upw, A.c, lo, hi, A.store_post ? 1 : 0, A.rhs_next,
                RS ? partials + kNormBlocks : (double *)nullptr, A.sa1, A.sb1, A.sa2, A.sb2);
     return (int)grid * 2 * WPB;
+}
+// the format of the launch (XArgs::pin / pout; step mode: always full)
+template <int WPB, int K, bool G, bool RS, bool SV, bool FM>
+static int xsmooth_launch_sv(const XArgs &A, const MarchRegions &reg, double *partials, int lo,
+                             int hi, long min_rows, long max_wgs, hipStream_t s) {
+    if constexpr (!RS) {
+        if (A.pin)
+            return xsmooth_launch_pk<WPB, K, G, RS, SV, FM, 2>(A, reg, partials, lo, hi, min_rows,
+                                                               max_wgs, s);
+        if (A.pout)
+            return xsmooth_launch_pk<WPB, K, G, RS, SV, FM, 1>(A, reg, partials, lo, hi, min_rows,
+                                                               max_wgs, s);
+    }
+    return xsmooth_launch_pk<WPB, K, G, RS, SV, FM, 0>(A, reg, partials, lo, hi, min_rows, max_wgs,
+                                                       s);
 }
 // SV when the level's velocity factors are given (XArgs::sa1); FM = the
 // level's fp_mode (Coef::fm)
@@ -981,6 +1245,11 @@ static int xsmooth_inst(const XArgs &A, hipStream_t s) {
     // the unguarded kernel's division assumes d > 0 (div_diag<true>)
     const bool split = g_xfast != 0 && A.c.dgs > 0;
     if (A.phase != 0 && !split) return -1;   // a split pass needs the split kernels
+    // the packed u_pre: whole levels as the two march launches (or the guarded
+    // one) only -- the caller asks xpack_supported first
+    if ((A.pin || A.pout) && (A.rb >= 0 || A.phase != 0 || A.band != 0 ||
+                              !xpack_supported(n, A.c.dgs)))
+        return -1;
     if (split && rb - ra <= g_xtile_max_rows) {
         const int r = xsmooth_tiled<WPB, K>(A, ra, rb, lo, hi, s);
         if (r != -2) return r;
@@ -1002,6 +1271,7 @@ static int xsmooth_inst(const XArgs &A, hipStream_t s) {
 
 int launch_xsmooth(const XArgs &A, int sweeps, hipStream_t s) {
     if (A.rb >= 0 && (A.ra & 1)) return -1;   // row blocks start at even rows
+    if ((A.pin || A.pout) && A.rhs_next) return -1;   // step mode: the full format
     int blocks = -1;
     // 4 strip pairs per workgroup (one workgroup of 8 waves per CU): adjacent
     // 1-KiB row pieces of four strips per load (measured: 4.05 ms vs 4.13 ms

@@ -213,6 +213,19 @@ int mgx_synchronize(mgx_ctx *ctx);
  * "xfast": 1 (default) runs the cross-cycle pass as an unguarded kernel over
  * the interior strips and rows plus a guarded kernel over the boundary strips
  * and bands; 0 = one guarded launch (bitwise the same results).
+ * "xpack": 1 = the cross-cycle pass hands the next cycle's pre-smoothed u on
+ * with one of its two colours only (half-pitch rows, 8 B per point pair) and
+ * the next pass rebuilds the other colour -- the pre-smoothing's last
+ * half-sweep again, from operands it reads anyway -- so a pass moves one finest
+ * array less (half written, half read); 0 = whole rows; 2 (default) = 1
+ * inside mgx_run_cycles in fp_mode fma (level 0 -4.8 % at N=16384), else 0:
+ * in the bitwise mode the rebuilt colour's division makes the pass 5 %
+ * slower, and mg_outer / step end in a pass that needs whole rows, so a
+ * packed u_pre would cost them an expansion pass per call.  Bitwise the same
+ * results.  Whole levels run as row marches only (not the LDS-tile
+ * form of "xtile_max_rows", nor step mode, nor partitioned contexts); a pass
+ * that needs whole rows after a packed one (the last cycle's plain
+ * post-smoothing, a recomputed u_post) expands it first.
  * "march_tile_rows": a row block whose wave march would give each resident
  * workgroup fewer than this many rows runs as LDS tiles (default 16, >= 0).
  * "xtile_max_rows": on row blocks of at most this many rows (a rank of a

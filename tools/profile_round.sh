@@ -18,10 +18,13 @@ cp "$(find "$OUT/trace" -name 'run_kernel_stats.csv' | head -1)" "$OUT/kernel_st
 rm -rf "$OUT/trace"
 # PMC per arithmetic mode, the bench's cycle pattern (one run_cycles(10) call):
 # fma (the headline), bitwise, fma on the generic velocity path
-for mode in fma bitwise fma-generic; do
-  fp=${mode%-generic}
+# (fma-xpack: the headline mode with the packed u_pre, tuning key xpack = 1 --
+# the k_xsmooth_fp / k_xsmooth_pp kernels; bench.py reads the other three)
+for mode in fma bitwise fma-generic fma-xpack; do
+  fp=${mode%-generic}; fp=${fp%-xpack}
   gen=0; [ "$mode" = "fma-generic" ] && gen=1
-  bash tools/pmc_collect.sh "$OUT/pmc_$mode" 16384 9 10 $fp $gen
+  xp=0; [ "$mode" = "fma-xpack" ] && xp=1
+  bash tools/pmc_collect.sh "$OUT/pmc_$mode" 16384 9 10 $fp $gen $xp
   python3 tools/pmc_summary.py "$OUT/pmc_$mode" > "$OUT/pmc_$mode.json"
   MGX_PMC_MODE=$mode python3 tools/hbm_traffic.py "$OUT/pmc_$mode.json" > "$OUT/hbm_traffic_$mode.json"
   rm -rf "$OUT/pmc_$mode"
