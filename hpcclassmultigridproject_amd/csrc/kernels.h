@@ -147,8 +147,18 @@ struct SmoothArgs {
     // (launch_smooth / launch_smooth_wpair return -4 when the pass would
     // march instead)
     CoarseFuse cf{};
+    // One colour of the pre-smoothed u between a level's two passes (wsmooth.hip
+    // PK, tuning key "wpack"; levels >= 1, whole level, sweeps 2-3): pout = the
+    // kModeZero | kModeRestrict pass writes only the points with (row + column)
+    // odd, as half-pitch rows in the first half of uout; pin = uin of the
+    // kModeProlong pass holds that.  Marches only: launch_smooth returns -1
+    // (nothing launched) for any other pass -- ask smooth_packs first.
+    bool pin = false, pout = false;
 };
 int launch_smooth(const SmoothArgs &a, int sweeps, int mode, hipStream_t s);
+// whether both the kModeZero | kModeRestrict and the kModeProlong pass of
+// `sweeps` sweeps on a's whole level run as wave marches (the packed form)
+bool smooth_packs(const SmoothArgs &a, int sweeps);
 // A W-cycle's post-smoothing of one visit + pre-smoothing of the next on a tile
 // level as one pass (prolongation+add, 2 nsmooth sweeps, restriction); -1 if
 // the level marches or nsmooth is not 1..3.

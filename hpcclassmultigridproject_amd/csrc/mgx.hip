@@ -159,11 +159,13 @@ int prof_flush(mgx_ctx *c) {
 }
 
 // ---------------------------------------------------------------- level ops
+static int op_wexpand(mgx_ctx *c, int l);
 int materialize(mgx_ctx *c, int l) {
     Level &L = c->lv[l];
-    if (!L.zero) return MGX_OK;
+    if (!L.zero) return op_wexpand(c, l);   // (whole rows for whoever reads them)
     HIPCHK(hipMemsetAsync(L.U(), 0, sizeof(double) * L.pitch * (L.n + 1), c->stream));
     L.zero = false;
+    if (l >= 1) L.packed[L.cur] = false;
     return MGX_OK;
 }
 
@@ -247,10 +249,56 @@ static void took_coarse(mgx_ctx *c, int l) {
     c->lv[l + 1].zero = false;
 }
 
+// tuning key "wpack": levels >= 1, whose pre- and post-smoothing are wave
+// marches, pass the pre-smoothed u between the two as one colour (wsmooth.hip
+// PK): 0 whole rows, 1 packed wherever that form exists, 2 packed in fp_mode
+// fma only.  Level::packed[i] of a level >= 1 marks u[i] as such a buffer; it
+// is set by the pre-smoothing of op_vcycle alone (pack_out) and consumed by
+// the same call's post-smoothing; any other reader gets whole rows first
+// (op_wexpand).  3 (test hook): packed as 1, and every post-smoothing takes
+// the expansion path.  Default 2 -- measured at N=16384, L=9, alternated in
+// one process: fma level 1 0.610-0.613 -> 0.550-0.555 ms and the V-cycle 2.42-
+// 2.55 -> 2.34-2.35 ms; bitwise (division bound) level 1 0.721-0.723 -> 0.715-
+// 0.721 ms, inside the spread.
+long g_wpack = 2;
+static bool wpack_on(const Level &L) {
+    return g_wpack == 1 || g_wpack == 3 || (g_wpack == 2 && L.coef.fm);
+}
+
+// Whole rows in place of level l's packed pre-smoothed u: the pre-smoothing
+// (from zero, without its restriction) once more into the same buffer -- the
+// colour that was dropped cannot be rebuilt from the kept one, and no default
+// path comes here (a post-smoothing that turned out not to be a packed march)
+static int op_wexpand(mgx_ctx *c, int l) {
+    Level &L = c->lv[l];
+    if (l < 1 || !L.packed[L.cur]) return MGX_OK;
+    const int k = c->opt.nsmooth;
+    mgx::SmoothArgs A{};
+    A.uin = L.u[L.cur];
+    A.uout = L.u[L.cur];
+    A.rhs = L.rhs;
+    A.v1 = L.v1;
+    A.v2 = L.v2;
+    A.zrow = c->zrow;
+    A.vz = L.vz;
+    A.n = L.n;
+    A.pitch = L.pitch;
+    A.c = L.coef;
+    A.partials = c->partials;
+    A.norm_out = c->dscal;
+    int blocks = 0;
+    CHK(launch(c, MGX_K_GS, l, 40.0 * k * L.M(), 8.0 * (2.0 * L.M() + 2.0 * L.Mv()),
+               [&] { blocks = mgx::launch_smooth(A, k, mgx::kModeZero, c->stream); }));
+    if (blocks < 0) return fail(MGX_E_INTERNAL, "op_wexpand: unsupported sweeps");
+    L.packed[L.cur] = false;
+    return MGX_OK;
+}
+
 int op_smooth(mgx_ctx *c, int l, int sweeps, bool prolong, bool restrict_, bool norm,
-              bool *fused_norm) {
+              bool *fused_norm, bool pack_out = false) {
     Level &L = c->lv[l];
     if (fused_norm) *fused_norm = false;
+    if (c->opt.smoother != 0 || sweeps <= 0) CHK(op_wexpand(c, l));   // (whole rows below)
     if (c->opt.smoother == 0 && sweeps > 0) {
         const int fuse = std::max(1, std::min(c->opt.fuse, mgx::kSmoothMaxSweeps));
         int done = 0;
@@ -290,6 +338,16 @@ int op_smooth(mgx_ctx *c, int l, int sweeps, bool prolong, bool restrict_, bool 
             A.partials = c->partials;
             A.norm_out = c->dscal;
             if (cfuse) take_coarse(c, l, A);
+            // (wpack: both passes of the level must be marches; a packed input
+            // whose pass is none after all is expanded in place first)
+            const bool pk_form = l >= 1 && !c->dist && first && last && (k == 2 || k == 3) &&
+                                 mgx::smooth_packs(A, k);
+            if (l >= 1 && L.packed[L.cur] &&
+                (!(pk_form && mode == mgx::kModeProlong) || g_wpack == 3))
+                CHK(op_wexpand(c, l));
+            A.pin = l >= 1 && L.packed[L.cur];
+            A.pout = pack_out && pk_form && wpack_on(L) &&
+                     mode == (mgx::kModeZero | mgx::kModeRestrict);
             double bytes = 40.0 * k * L.M();
             int kind = MGX_K_GS;
             if (pr) {
@@ -303,9 +361,11 @@ int op_smooth(mgx_ctx *c, int l, int sweeps, bool prolong, bool restrict_, bool 
             // (v1 / v2 rows >= vz come from the zero row, not HBM)
             // (generated velocity: the 3-sweep pre / post marches, launch_smooth)
             const bool vgu = mgx::smooth_generates_velocity(A, k, mode);
+            // (a packed pre-smoothed u: half a level array per packed side)
             const double cbytes = 8.0 * (((mode & mgx::kModeZero) ? 2.0 : 3.0) * L.M() +
                                          (vgu ? 0.0 : 2.0 * L.Mv()) +
-                                         ((pr ? 1 : 0) + (rs ? 1 : 0)) * c->lv[l + 1].M());
+                                         ((pr ? 1 : 0) + (rs ? 1 : 0)) * c->lv[l + 1].M() -
+                                         0.5 * L.M() * ((A.pin ? 1 : 0) + (A.pout ? 1 : 0)));
             int blocks = 0;
             CHK(check_coarse_rhs(A, mode));
             const size_t before = c->pending.size();
@@ -324,8 +384,9 @@ int op_smooth(mgx_ctx *c, int l, int sweeps, bool prolong, bool restrict_, bool 
                 took_coarse(c, l);
             }
             if (blocks < 0) return fail(MGX_E_ARG, "launch_smooth: unsupported sweeps/mode");
+            if (l >= 1) L.packed[L.cur] = false;   // (a packed input: consumed)
             L.cur = L.nxt();
-            L.packed[L.cur] = false;   // (whole rows written)
+            L.packed[L.cur] = A.pout;   // (else whole rows written)
             L.zero = false;
             if (rs) c->lv[l + 1].zero = true;
             if (nm && fused_norm) *fused_norm = true;
@@ -416,6 +477,7 @@ int op_wpair(mgx_ctx *c, int l, bool *done) {
     const int k = c->opt.nsmooth;
     if (!g_wpair || c->opt.smoother != 0 || k < 1 || k > 3 || c->opt.fuse < k || L.zero)
         return MGX_OK;
+    if (L.packed[L.cur]) return MGX_OK;   // (a march level's packed u: the two passes)
     // The coarsest solve pending, fused: its workgroups read Cl.rhs at their
     // start while the pass's restriction stores the next visit's rhs, so that
     // goes to the level's second rhs buffer (swapped in after the launch);
@@ -775,8 +837,11 @@ int op_vcycle(mgx_ctx *c, int l, double *norm, bool store_post) {
                 CHK(op_coarse(c, l, c->opt.shape));
             }
         } else {
+            // (the next reader of u[l] is this visit's post-smoothing below:
+            // levels >= 1 may hand it over as one colour, "wpack")
             if (!pre_done)
-                CHK(op_smooth(c, l, c->opt.nsmooth, false, /*restrict=*/true, false, nullptr));
+                CHK(op_smooth(c, l, c->opt.nsmooth, false, /*restrict=*/true, false, nullptr,
+                              /*pack_out=*/l >= 1));
             pre_done = false;
             CHK(op_vcycle(c, l + 1));
             // W-cycles: this visit's post- and the next visit's pre-smoothing
@@ -2384,6 +2449,11 @@ extern "C" int mgx_set_tuning(const char *key, long value) {
         mgxi::g_xpack = value;
         return MGX_OK;
     }
+    if (!strcmp(key, "wpack")) {
+        if (value < 0 || value > 3) return fail(MGX_E_ARG, "wpack must be 0, 1, 2 or 3");
+        mgxi::g_wpack = value;
+        return MGX_OK;
+    }
     if (!strcmp(key, "tile32_min_n")) {
         if (value < 0) return fail(MGX_E_ARG, "tile32_min_n must be >= 0");
         mgx::set_tile32_min_n(value);
@@ -2516,6 +2586,10 @@ extern "C" int mgx_get_tuning(const char *key, long *value) {
     }
     if (!strcmp(key, "xpack")) {
         *value = mgxi::g_xpack;
+        return MGX_OK;
+    }
+    if (!strcmp(key, "wpack")) {
+        *value = mgxi::g_wpack;
         return MGX_OK;
     }
     if (!strcmp(key, "xfast")) {

@@ -9,6 +9,15 @@
 namespace mgx {
 namespace {
 
+// st2_if's streaming store for one double (a packed row's element)
+__device__ __forceinline__ void st1s_if(double *row, int col, bool on, double v) {
+#if MGX_NTST
+    if (on) __builtin_nontemporal_store(v, row + col);
+#else
+    if (on) row[col] = v;
+#endif
+}
+
 template <int K, int MODE>
 struct SmoothCfg {
     static constexpr bool ZERO = (MODE & 1) != 0;
@@ -101,7 +110,20 @@ struct WCfg {
 // of the lane's two columns replace the two HBM row loads; the lane's sb pairs
 // (three states per column) sit in its LDS slice and are multiplied in at the
 // row's first use -- the same operands as the tower's entries, bitwise.
-template <int WPB, int K, int MODE, bool G, bool PD = false, bool FM = false, bool VG = false>
+// PK (tuning key "wpack"; levels >= 1, whose u starts from zero): the
+// pre-smoothing hands its u to the level's post-smoothing as one colour.  A
+// sweep's first half-sweep overwrites every interior point with (row + column)
+// even from its four neighbours, all odd; so of the pre-smoothed u the post
+// pass reads the odd colour only -- the one stage S-1 updated last -- and the
+// Dirichlet ring, which is +0.0 on these levels.  PK = 1 (the ZERO|REST pass)
+// stores just that colour: row R at half pitch, element j = the point
+// (R, 2j + 1 - (R & 1)), the lane's .y on even rows and .x on odd ones, in the
+// first half of uout.  PK = 2 (the PROL pass) loads those rows and takes the
+// other colour as +0.0 before the prolongation is added: exact on the ring,
+// dead everywhere else.  Nothing is rebuilt, the cone (E, H, W) and the work
+// split are those of the whole-row pass, and every stored bit is the same.
+template <int WPB, int K, int MODE, bool G, bool PD = false, bool FM = false, bool VG = false,
+          int PK = 0>
 __global__ __launch_bounds__(64 * WPB, (WCfg<K, MODE>::MINB)) void k_wsmooth(
     const double *__restrict__ uin, double *__restrict__ uout, const double *__restrict__ rhs,
     const double *__restrict__ v1, const double *__restrict__ v2, const double *__restrict__ uc,
@@ -131,6 +153,11 @@ __global__ __launch_bounds__(64 * WPB, (WCfg<K, MODE>::MINB)) void k_wsmooth(
     double acc = 0.0;
     // row offsets as 32 x 32 -> 64-bit products (pitches < 2^31 elements)
     const int ip = (int)pitch, ipc = (int)pitchc;
+    const int ihp = ip >> 1;   // pitch of a packed row (PK)
+    static_assert(PK == 0 || (G && !C::NORM && !C::RHSN &&
+                              (PK == 1 ? (C::ZERO && C::REST && !C::PROL)
+                                       : (C::PROL && !C::ZERO && !C::REST))),
+                  "packed rows: the guarded ZERO|REST pass writes them, the PROL pass reads them");
     auto rowoff = [](int r, int p) { return (long)r * (long)p; };
     int a = 0, b = 0;   // the segment's owned rows (set per segment below)
     // r in [a, b) as one unsigned compare (b >= a)
@@ -183,7 +210,10 @@ __global__ __launch_bounds__(64 * WPB, (WCfg<K, MODE>::MINB)) void k_wsmooth(
         auto load_u = [&](int R, UPre &u, const bool odd) {
             if (C::ZERO) return;
             const int Rc = min(max(R, lo), hi);
-            u.X = ld2((uin + rowoff(Rc, ip)) + cl);
+            if (PK == 2)   // (the row's odd colour, 8 B per lane)
+                u.X.x = ((uin + rowoff(Rc, ihp)) + (cl >> 1))[0];
+            else
+                u.X = ld2((uin + rowoff(Rc, ip)) + cl);
             if (C::PROL) {
                 const double *p0 = (uc + rowoff(Rc >> 1, ipc)) + jl;
                 u.q00 = p0[0];
@@ -202,6 +232,8 @@ __global__ __launch_bounds__(64 * WPB, (WCfg<K, MODE>::MINB)) void k_wsmooth(
         auto make_u = [&](int R, const UPre &u, const bool odd) {
             double2 v = u.X;
             if (C::ZERO) v = make_double2(0.0, 0.0);
+            // (column c0 of an odd row, c0 + 1 of an even one)
+            if (PK == 2) v = odd ? make_double2(u.X.x, 0.0) : make_double2(0.0, u.X.x);
             if (C::PROL) {
                 double2 pr;
                 const double q01 = (!G || j1) ? u.q01 : 0.0;
@@ -426,8 +458,12 @@ __global__ __launch_bounds__(64 * WPB, (WCfg<K, MODE>::MINB)) void k_wsmooth(
                 // (3) row s+2-S is final
                 {
                     const int ro = s + 2 - S;
-                    st2_if(uout + rowoff(ro, ip), c0, rowin(ro) && keep,
-                           ur[(p + 2 - S + 2 * NR) % NR]);
+                    const double2 uf = ur[(p + 2 - S + 2 * NR) % NR];
+                    if (PK == 1)   // (row parity = p's: static)
+                        st1s_if(uout + rowoff(ro, ihp), c0 >> 1, rowin(ro) && keep,
+                                (p & 1) ? uf.x : uf.y);
+                    else
+                        st2_if(uout + rowoff(ro, ip), c0, rowin(ro) && keep, uf);
                 }
                 // (4) residual stage on row s+1-S
                 if (C::REST || C::NORM) {
@@ -707,7 +743,7 @@ __global__ __launch_bounds__(MGX_TILE_THREADS) void k_smooth_tile(
 
 }  // namespace
 
-template <int WPB, int K, int MODE, bool G, bool PD, bool FM, bool VG>
+template <int WPB, int K, int MODE, bool G, bool PD, bool FM, bool VG, int PK>
 static int wsmooth_launch_pd(const SmoothArgs &A, const MarchRegions &reg, double *partials,
                              long max_wgs, hipStream_t s) {
     const long total = reg.pre[reg.count];
@@ -717,8 +753,8 @@ static int wsmooth_launch_pd(const SmoothArgs &A, const MarchRegions &reg, doubl
         int dev = 0, cus = 0, per = 0;
         (void)hipGetDevice(&dev);
         (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k_wsmooth<WPB, K, MODE, G, PD, FM, VG>,
-                                                           64 * WPB, 0);
+        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(
+            &per, k_wsmooth<WPB, K, MODE, G, PD, FM, VG, PK>, 64 * WPB, 0);
         slots = std::max(1, cus) * std::max(1, per);
     }
     long upw;
@@ -729,22 +765,22 @@ static int wsmooth_launch_pd(const SmoothArgs &A, const MarchRegions &reg, doubl
     // strips); the same per rank on 8 row blocks
     const unsigned grid = plan_march(reg, WPB, slots, get_march_min_rows(), max_wgs,
                                      WCfg<K, MODE>::E + WCfg<K, MODE>::NR / 2, upw, r);
-    MGX_LAUNCH((k_wsmooth<WPB, K, MODE, G, PD, FM, VG>), dim3(grid), dim3(64 * WPB), s, A.uin,
+    MGX_LAUNCH((k_wsmooth<WPB, K, MODE, G, PD, FM, VG, PK>), dim3(grid), dim3(64 * WPB), s, A.uin,
                A.uout, A.rhs, A.v1, A.v2, A.uc, A.pitchc, A.rhsc, partials, (int)A.n, A.pitch, r,
                upw, A.c, A.lo, A.hi, A.rhs_out, A.zrow ? A.zrow : A.v1,
                A.zrow ? A.vz : 0x7fffffff, A.vg);
     return (int)grid * WPB;   // NORM partials written
 }
 // the short division when the diagonal is positive (every nu <= 0)
-template <int WPB, int K, int MODE, bool G, bool VG = false>
+template <int WPB, int K, int MODE, bool G, bool VG = false, int PK = 0>
 static int wsmooth_launch(const SmoothArgs &A, const MarchRegions &reg, double *partials,
                           long max_wgs, hipStream_t s) {
     // (fp_mode fma: no division)
     if (A.c.fm)
-        return wsmooth_launch_pd<WPB, K, MODE, G, false, true, VG>(A, reg, partials, max_wgs, s);
+        return wsmooth_launch_pd<WPB, K, MODE, G, false, true, VG, PK>(A, reg, partials, max_wgs, s);
     if (A.c.dgs > 0)
-        return wsmooth_launch_pd<WPB, K, MODE, G, true, false, VG>(A, reg, partials, max_wgs, s);
-    return wsmooth_launch_pd<WPB, K, MODE, G, false, false, VG>(A, reg, partials, max_wgs, s);
+        return wsmooth_launch_pd<WPB, K, MODE, G, true, false, VG, PK>(A, reg, partials, max_wgs, s);
+    return wsmooth_launch_pd<WPB, K, MODE, G, false, false, VG, PK>(A, reg, partials, max_wgs, s);
 }
 
 // One guarded launch over the whole level.  (The interior / edge split that
@@ -756,6 +792,22 @@ static int smooth_winst(const SmoothArgs &A, hipStream_t s) {
     using C = WCfg<K, MODE>;
     MarchRegions inner, edge;
     march_regions<WPB>(A.n, C::W, C::H, A.ra, A.rb, C::TOP, C::BOT, false, inner, edge);
+    // packed rows (PK of k_wsmooth): written by the 2- and 3-sweep ZERO|REST
+    // pass, read by the PROL pass; no other pass has the form
+    constexpr int PK = (K < 2) ? 0
+                       : MODE == (kModeZero | kModeRestrict) ? 1
+                       : MODE == kModeProlong ? 2 : 0;
+    const bool pk = PK == 1 ? A.pout : A.pin;
+    if ((A.pin || A.pout) && (PK == 0 || !pk)) return -1;
+    if constexpr (PK != 0) {
+        if (pk) {
+            if constexpr (K == 3)
+                if (A.vg.a) return wsmooth_launch<WPB, K, MODE, true, true, PK>(
+                                A, edge, A.partials, kNormBlocks / WPB, s);
+            return wsmooth_launch<WPB, K, MODE, true, false, PK>(A, edge, A.partials,
+                                                                 kNormBlocks / WPB, s);
+        }
+    }
     // the generated velocity: the V-cycle's 3-sweep pre / post passes (and a
     // W-cycle's second pre-smoothing of a visit, from a non-zero u)
     if constexpr (K == 3 && (MODE == (kModeZero | kModeRestrict) || MODE == kModeProlong ||
@@ -844,6 +896,8 @@ static int smooth_block(const SmoothArgs &A, hipStream_t s) {
     // a fused coarse solve needs the tile pass (the march reads uc from HBM)
     const bool fused = A.cf.on && (MODE & kModeProlong) && A.cf.n <= kCoarseLdsMaxN;
     if (A.cf.on && !fused) return -4;
+    // packed rows are a march's (the caller asks smooth_packs first)
+    if ((A.pin || A.pout) && tile) return -1;
     if (tile) {
         const int g = smooth_tile_inst<K, MODE>(A, s);
         if (g > 0) return g;
@@ -880,6 +934,17 @@ bool smooth_generates_velocity(const SmoothArgs &A0, int sweeps, int mode) {
     if (mode == (kModeZero | kModeRestrict)) return !smooth_as_tiles<3, kModeZero | kModeRestrict>(A);
     if (mode == kModeProlong) return !smooth_as_tiles<3, kModeProlong>(A);
     if (mode == kModeRestrict) return !smooth_as_tiles<3, kModeRestrict>(A);
+    return false;
+}
+
+bool smooth_packs(const SmoothArgs &A0, int sweeps) {
+    SmoothArgs A = A0;
+    if (A.rb >= 0) return false;   // whole levels only
+    A.ra = 0;
+    A.rb = (int)A.n + 1;
+    constexpr int PRE = kModeZero | kModeRestrict, POST = kModeProlong;
+    if (sweeps == 2) return !smooth_as_tiles<2, PRE>(A) && !smooth_as_tiles<2, POST>(A);
+    if (sweeps == 3) return !smooth_as_tiles<3, PRE>(A) && !smooth_as_tiles<3, POST>(A);
     return false;
 }
 

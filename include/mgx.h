@@ -226,6 +226,17 @@ int mgx_synchronize(mgx_ctx *ctx);
  * form of "xtile_max_rows", nor step mode, nor partitioned contexts); a pass
  * that needs whole rows after a packed one (the last cycle's plain
  * post-smoothing, a recomputed u_post) expands it first.
+ * "wpack": the levels below the finest whose pre- and post-smoothing both run
+ * as wave marches (whole levels, nsmooth 2 or 3 in one pass, not partitioned):
+ * 1 = the pre-smoothing stores only the colour its last half-sweep updated
+ * (half-pitch rows) and the level's post-smoothing, the buffer's only reader,
+ * loads just that: the post-smoothing's first half-sweep overwrites the other
+ * colour without reading it, and the Dirichlet ring of these levels is zero,
+ * so nothing is rebuilt and each of the two passes moves half a level array
+ * less.  0 = whole rows; 2 = 1 in fp_mode fma only.  Bitwise the same results.
+ * A post-smoothing that turns out not to be such a march gets whole rows
+ * first (the pre-smoothing run again without its restriction); 3 is a test
+ * hook: packed as 1, and every post-smoothing takes that expansion.
  * "march_tile_rows": a row block whose wave march would give each resident
  * workgroup fewer than this many rows runs as LDS tiles (default 16, >= 0).
  * "xtile_max_rows": on row blocks of at most this many rows (a rank of a
