@@ -20,6 +20,7 @@ FP_BITWISE, FP_FMA = 0, 1   # mgx_options.fp_mode
 UNIQUE_ID_BYTES = 128   # MGX_UNIQUE_ID_BYTES (ncclUniqueId)
 MGX_SOURCE_MAX_TERMS = 4   # terms of a separable source (mgx_set_source_separable)
 SOURCE_NONE, SOURCE_FIELD, SOURCE_SEPARABLE = 0, 1, 2   # mgx_source_kind
+BC_NOW, BC_NEXT_STEP = 0, 1   # mgx_set_boundary `when`
 K_GS, K_RESTRICT, K_PROLONG, K_RESNORM, K_COARSE, K_RHS, K_HALO, K_PSMOOTH, K_XSMOOTH = range(9)
 KERNEL_NAMES = {K_GS: "gs_sweep", K_RESTRICT: "residual_restrict", K_PROLONG: "prolong_add",
                 K_RESNORM: "residual_norm", K_COARSE: "coarse_solve", K_RHS: "compute_rhs",
@@ -139,6 +140,12 @@ _SIGS = {
     "mgx_sample": (_I, [_vp, _I, _I, _L, _vp]),
     "mgx_sample_device": (_I, [_vp, _I, _I, _L, _vp]),
     "mgx_sample_rows": (_I, [_vp, _I, _I, _L, _vp, C.POINTER(_L), C.POINTER(_L)]),
+    "mgx_set_boundary": (_I, [_vp, _vp, _I]),
+    "mgx_set_boundary_device": (_I, [_vp, _vp, _I]),
+    "mgx_get_boundary": (_I, [_vp, _vp]),
+    "mgx_get_boundary_device": (_I, [_vp, _vp]),
+    "mgx_boundary_info": (_I, [_vp, C.POINTER(_I)]),
+    "mgx_write_boundary": (_I, [_vp, _L, _vp]),
     "mgx_build_id": (C.c_char_p, []),
     "mgx_build_sources_id": (C.c_char_p, []),
 }
@@ -243,6 +250,15 @@ def device_ptr(x, count, what="tensor"):
     if x.numel() < count or not x.is_contiguous() or x.element_size() != 8:
         raise ValueError(f"{what}: expected a contiguous float64 tensor of {count} entries")
     return x.data_ptr()
+
+
+def write_boundary(u, n, g):
+    """mgx_write_boundary: the ring of u = g on device tensors (or raw device
+    pointers) -- u in the reference layout ((n+1)^2 float64, any n >= 1), g
+    4(n+1) float64, side-major: rows 0 and n, then columns 0 and n; the
+    corners are the rows'.  The interior of u is untouched.  Null stream."""
+    check(lib().mgx_write_boundary(device_ptr(u, (n + 1) * (n + 1), "u"), n,
+                                   device_ptr(g, 4 * (n + 1), "g")))
 
 
 def array_stats(a, n, interior=False, minus=None) -> Stats:

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/mgx.h"
+#include "boundary.h"
 #include "diag.h"
 #include "kernels.h"
 
@@ -112,6 +113,14 @@ struct mgx_ctx {
     // scratch of the field diagnostics (diag.h: partial records + the result),
     // allocated by the first statistics call
     void *diag = nullptr;
+    // mgx_set_boundary: two rings of 4(N+1) doubles, allocated by the first
+    // call that needs one -- [0] the pending ring of MGX_BC_NEXT_STEP
+    // (bc_pending: the next mgx_step consumes it), [1] the staging of a host
+    // ring written now and of mgx_get_boundary.  A partitioned context keeps
+    // them here too: its parts and sub-contexts share the device and stream.
+    double *bc_buf = nullptr;
+    bool bc_pending = false;
+    mgxbc::RingTimer bc_timer;   // tuning key "boundary_us"
     mgxi::Dist *dist = nullptr;   // row-partitioned multi-GPU state (dist.hip)
     // mg_outer's cycle predicted to be the last: its finest level runs the
     // post-smoothing alone, not the cross pass (no next-cycle pre-smoothing)
@@ -233,6 +242,21 @@ int copy_source_factors(double **da, double **db, long n, long pitch, int terms,
 // tuning key "source_sv" (mgx.hip): the source pass reads the finest level's
 // velocity factors, where the context keeps them, instead of the 2-D v1 / v2
 extern long g_source_sv;
+
+// mgx_set_boundary(MGX_BC_NOW) on a single-GPU context (mgx.hip; csrc/
+// boundary.hip).  boundary_prepare_ctx: the finest u in full form in its
+// current buffer, and everything formed with the old ring dropped;
+// boundary_scatter_ctx: the ring g (device) into that buffer on c's stream.
+// Neither synchronises.
+int boundary_prepare_ctx(mgx_ctx *c);
+int boundary_scatter_ctx(mgx_ctx *c, const double *g);
+// ... and on a partitioned context (dist.hip): every part's allocated rows, or
+// every sub-context where all levels are replicated; timed by c->bc_timer
+int dist_boundary_now(mgx_ctx *c, const double *g);
+// mgx_get_boundary of a local-parts context: each part's owned rows into g
+// (device); an RCCL rank: MGX_E_ARG (who: the C entry point, for the message),
+// checked before any device call
+int dist_boundary_gather(mgx_ctx *c, double *g, const char *who);
 
 // Field diagnostics (mgx.hip; csrc/diag.hip), shared with dist.hip.
 // The statistics of rows [r0, r1) of a field on c's stream and scratch;

@@ -1263,6 +1263,79 @@ void dist_set_source_scale(mgx_ctx *c, double s) {
     drop_source_state(c);
 }
 
+// mgx_set_boundary(MGX_BC_NOW) on a partitioned context: g is the whole ring
+// on the device.  Every part writes columns 0 and n of all its allocated rows
+// [lo, hi] -- its ghost rows take the values their owners write, so no
+// exchange follows and an early exchange of the buffer stays valid -- and rows
+// 0 / n where it holds them.  With every level replicated each sub-context is
+// written.  The speculative states go as in dist_drop_spec /
+// dist_set_source_scale.  Only the current buffer is written: a part's pass
+// writes its owned rows whole from its input, and the ghost rows arrive as
+// whole rows from their owners.
+int dist_boundary_now(mgx_ctx *c, const double *g) {
+    Dist *d = c->dist;
+    HIPCHK(hipSetDevice(c->device));
+    CHK(settle(c));
+    for (auto &p : d->parts) {
+        if (!p.lv.empty()) {
+            p.lv[0].spec = -1;
+            p.lv[0].xin = -1;
+        }
+        if (p.sub) {
+            if (d->la == 0) {
+                CHK(boundary_prepare_ctx(p.sub));
+            } else {
+                drop_source_state(p.sub);
+                p.sub->cf_level = -1;
+                p.sub->cf_reps = 0;
+            }
+        }
+    }
+    drop_source_state(c);
+    c->bc_timer.begin(c->stream);
+    int rc = MGX_OK;
+    for (auto &p : d->parts) {
+        if (rc != MGX_OK) break;
+        if (d->la == 0) {
+            rc = boundary_scatter_ctx(p.sub, g);
+            continue;
+        }
+        PLevel &L = p.lv[0];
+        mgxbc::launch_scatter(L.u[L.cur], L.pitch, L.n, L.lo, L.hi, g, c->stream);
+        rc = check_launch("mgx_set_boundary: ring scatter");
+    }
+    c->bc_timer.end(c->stream);
+    return rc;
+}
+
+// mgx_get_boundary of a local-parts context: every part gathers its owned rows
+// [ra, rb) (row 0 lies in the first part, row n in the last) into the one ring
+// g on the device; with every level replicated, sub-context 0's full copy.
+// g == nullptr: the argument checks alone, before any device call.
+int dist_boundary_gather(mgx_ctx *c, double *g, const char *who) {
+    Dist *d = c->dist;
+    if (!d->local)
+        return fail(MGX_E_ARG, std::string(who) + ": not available on an RCCL rank (it would need "
+                                                  "communication: use mgx_download_rows or "
+                                                  "mgx_sample_rows)");
+    if (!g) return MGX_OK;
+    CHK(settle(c));
+    if (d->la == 0) {
+        mgx_ctx *s = d->parts[0].sub;
+        CHK(materialize(s, 0));
+        CHK(op_expand(s));
+        Level &L = s->lv[0];
+        mgxbc::launch_gather(L.U(), L.pitch, L.n, 0, 0, L.n, g, c->stream);
+        return check_launch(who);
+    }
+    for (auto &p : d->parts) {
+        PLevel &L = p.lv[0];
+        mgxbc::launch_gather(L.u[L.cur], L.pitch, L.n, L.lo, L.ra, L.rb - 1, g, c->stream);
+        CHK(check_launch(who));
+    }
+    return MGX_OK;
+}
+
 // mgx_synchronize of a partitioned context: the side stream's pending
 // exchanges are joined into the compute stream first, so that once the host
 // has synchronised it, no RCCL operation of this rank is in flight (a caller's
@@ -1998,6 +2071,7 @@ int mgx_dist_rows(mgx_ctx *c, int part, int *lo, int *hi) {
 int mgx_upload_rows(mgx_ctx *c, const double *const *u0, const double *const *v1,
                     const double *const *v2) {
     if (!c || !c->dist) return fail(MGX_E_ARG, "mgx_upload_rows: not a partitioned context");
+    c->bc_pending = false;   // a pending ring belongs to the old u (mgx_upload)
     return dist_upload_rows_impl(c, u0, v1, v2);
 }
 

@@ -1250,6 +1250,8 @@ void free_ctx(mgx_ctx *c) {
     (void)hipFree(c->src_a);
     (void)hipFree(c->src_b);
     (void)hipFree(c->diag);
+    (void)hipFree(c->bc_buf);
+    c->bc_timer.destroy();
     if (c->hscal) (void)hipHostFree(c->hscal);
     for (auto &r : c->pending) {
         (void)hipEventDestroy(r.e0);
@@ -1746,11 +1748,15 @@ int mgx_compute_rhs_source(double *rhs, const double *u, long n, const double *v
     return check_launch("mgx_compute_rhs_source");
 }
 
+// (a pending ring, mgx_set_boundary(MGX_BC_NEXT_STEP), belongs to the old u:
+// every upload cancels it)
 int mgx_upload(mgx_ctx *c, const double *u0, const double *v1, const double *v2) {
+    if (c) c->bc_pending = false;
     if (c && c->dist) return dist_upload(c, u0, v1, v2, hipMemcpyHostToDevice);
     return upload_ctx(c, u0, v1, v2, hipMemcpyHostToDevice);
 }
 int mgx_upload_device(mgx_ctx *c, const double *u0, const double *v1, const double *v2) {
+    if (c) c->bc_pending = false;
     if (c && c->dist) return dist_upload(c, u0, v1, v2, hipMemcpyDeviceToDevice);
     return upload_ctx(c, u0, v1, v2, hipMemcpyDeviceToDevice);
 }
@@ -1995,6 +2001,150 @@ int mgx_sample_rows(mgx_ctx *c, int part, int field, long stride, double *out, l
     return sample_impl(c, 0, field, stride, out, false, "mgx_sample_rows");
 }
 
+}  // extern "C"
+
+// ---- time-dependent Dirichlet data (include/mgx.h, csrc/boundary.hip)
+// Everything formed with the old ring goes -- what mgx_set_source drops, and a
+// deferred coarsest solve -- after a packed u_pre has been expanded, so that
+// the current buffer holds whole rows for the scatter.  Captured sub-cycles
+// stay: they hold no finest-level value.
+int mgxi::boundary_prepare_ctx(mgx_ctx *c) {
+    CHK(materialize(c, 0));
+    CHK(op_expand(c));
+    drop_source_state(c);
+    c->cf_level = -1;
+    c->cf_reps = 0;
+    return MGX_OK;
+}
+// Only the current buffer is written: every pass that writes a finest-level u
+// buffer writes its ring from its input (kernels.h launch_smooth: every point
+// of uout, boundary included; xsmooth.hip: the guarded kernel owns the whole
+// boundary and takes it from its input), never from what the output held.
+int mgxi::boundary_scatter_ctx(mgx_ctx *c, const double *g) {
+    Level &L = c->lv[0];
+    mgxbc::launch_scatter(L.U(), L.pitch, L.n, 0, L.n, g, c->stream);
+    return check_launch("mgx_set_boundary: ring scatter");
+}
+
+// MGX_BC_NOW with a device ring on any context; c->bc_timer spans the scatter
+// launches (committed by the caller once the stream has passed them)
+static int boundary_now(mgx_ctx *c, const double *g) {
+    if (c->dist) return dist_boundary_now(c, g);
+    CHK(boundary_prepare_ctx(c));
+    c->bc_timer.begin(c->stream);
+    const int rc = boundary_scatter_ctx(c, g);
+    c->bc_timer.end(c->stream);
+    return rc;
+}
+
+// the context's two rings (ctx.h bc_buf), allocated by the first call that needs one
+static int bc_buffers(mgx_ctx *c, const char *who) {
+    if (c->bc_buf) return MGX_OK;
+    const hipError_t e = hipMalloc(&c->bc_buf, sizeof(double) * 2 * (size_t)mgxbc::ring_size(c->N));
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        c->bc_buf = nullptr;
+        return fail(MGX_E_HIP, std::string(who) + ": no room for the context's copy of the ring: " +
+                                   hipGetErrorString(e));
+    }
+    return MGX_OK;
+}
+
+static int set_boundary_impl(mgx_ctx *c, const double *g, int when, hipMemcpyKind kind,
+                             const char *who) {
+    if (!c) return fail(MGX_E_ARG, std::string(who) + ": null ctx");
+    if (when != MGX_BC_NOW && when != MGX_BC_NEXT_STEP)
+        return fail(MGX_E_ARG, std::string(who) + ": when must be MGX_BC_NOW or MGX_BC_NEXT_STEP");
+    if (!g) {
+        if (when == MGX_BC_NOW) return fail(MGX_E_ARG, std::string(who) + ": null ring");
+        c->bc_pending = false;   // cancels a pending ring
+        return MGX_OK;
+    }
+    HIPCHK(hipSetDevice(c->device));
+    const size_t bytes = sizeof(double) * (size_t)mgxbc::ring_size(c->N);
+    if (when == MGX_BC_NEXT_STEP) {
+        CHK(bc_buffers(c, who));
+        // a prepared next step took its initial norm and its pre-smoothing with
+        // the old ring
+        if (c->step_spec) drop_spec(c);
+        c->bc_pending = false;
+        HIPCHK(hipMemcpyAsync(c->bc_buf, g, bytes, kind, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));   // the caller's buffer is free on return
+        c->bc_pending = true;
+        return MGX_OK;
+    }
+    const double *dg = g;
+    if (kind == hipMemcpyHostToDevice) {
+        CHK(bc_buffers(c, who));
+        double *stage = c->bc_buf + mgxbc::ring_size(c->N);
+        HIPCHK(hipMemcpyAsync(stage, g, bytes, kind, c->stream));
+        dg = stage;
+    }
+    CHK(boundary_now(c, dg));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    c->bc_timer.commit();
+    return MGX_OK;
+}
+
+static int get_boundary_impl(mgx_ctx *c, double *g, hipMemcpyKind kind, const char *who) {
+    if (!c) return fail(MGX_E_ARG, std::string(who) + ": null ctx");
+    if (!g) return fail(MGX_E_ARG, std::string(who) + ": null ring");
+    const bool host = kind == hipMemcpyDeviceToHost;
+    double *dg = g;
+    if (c->dist) {
+        CHK(dist_boundary_gather(c, nullptr, who));   // (the checks alone)
+        HIPCHK(hipSetDevice(c->device));
+        if (host) {
+            CHK(bc_buffers(c, who));
+            dg = c->bc_buf + mgxbc::ring_size(c->N);
+        }
+        CHK(dist_boundary_gather(c, dg, who));
+    } else {
+        HIPCHK(hipSetDevice(c->device));
+        if (host) {
+            CHK(bc_buffers(c, who));
+            dg = c->bc_buf + mgxbc::ring_size(c->N);
+        }
+        CHK(materialize(c, 0));
+        CHK(op_expand(c));   // as mgx_download
+        Level &L = c->lv[0];
+        mgxbc::launch_gather(L.U(), L.pitch, L.n, 0, 0, L.n, dg, c->stream);
+        CHK(check_launch(who));
+    }
+    if (host)
+        HIPCHK(hipMemcpyAsync(g, dg, sizeof(double) * (size_t)mgxbc::ring_size(c->N), kind,
+                              c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return MGX_OK;
+}
+
+extern "C" {
+
+int mgx_set_boundary(mgx_ctx *c, const double *g, int when) {
+    return set_boundary_impl(c, g, when, hipMemcpyHostToDevice, "mgx_set_boundary");
+}
+int mgx_set_boundary_device(mgx_ctx *c, const double *g, int when) {
+    return set_boundary_impl(c, g, when, hipMemcpyDeviceToDevice, "mgx_set_boundary_device");
+}
+int mgx_get_boundary(mgx_ctx *c, double *g) {
+    return get_boundary_impl(c, g, hipMemcpyDeviceToHost, "mgx_get_boundary");
+}
+int mgx_get_boundary_device(mgx_ctx *c, double *g) {
+    return get_boundary_impl(c, g, hipMemcpyDeviceToDevice, "mgx_get_boundary_device");
+}
+int mgx_boundary_info(mgx_ctx *c, int *pending) {
+    if (!c) return fail(MGX_E_ARG, "mgx_boundary_info: null ctx");
+    if (!pending) return fail(MGX_E_ARG, "mgx_boundary_info: null argument");
+    *pending = c->bc_pending ? 1 : 0;
+    return MGX_OK;
+}
+int mgx_write_boundary(double *u, long n, const double *g) {
+    if (!u || !g) return fail(MGX_E_ARG, "mgx_write_boundary: null pointer");
+    if (n < 1) return fail(MGX_E_ARG, "mgx_write_boundary: n must be >= 1");
+    mgxbc::launch_scatter(u, n + 1, n, 0, n, g, nullptr);
+    return check_launch("mgx_write_boundary");
+}
+
 static int no_dist(mgx_ctx *c, const char *what) {
     return fail(MGX_E_ARG, std::string(what) + ": per-level ops are not available on a "
                                                "partitioned context (use vcycle/mg_outer/step)");
@@ -2083,6 +2233,20 @@ static int step_impl(mgx_ctx *c, double tol, int *cycles, bool prepare_next,
     // multigrid.cpp:168-170), with the first pre-smoothing where it fuses --
     // or already done by the previous step's last cross pass
     double res0 = 0;
+    if (c->bc_pending) {
+        // a pending ring (mgx_set_boundary, MGX_BC_NEXT_STEP): the rhs with the
+        // old ring, the new ring, then mg_outer with its own initial norm --
+        // mgx_rhs; mgx_set_boundary(MGX_BC_NOW); mgx_mg_outer, launch for
+        // launch.  No fusion across the ring write, and no next step prepared:
+        // its ring will be set again.
+        CHK(c->dist ? dist_rhs(c) : op_rhs(c));
+        c->bc_pending = false;
+        CHK(boundary_now(c, c->bc_buf));
+        drop_step_spec(c);
+        const int rc = op_mg_outer(c, tol, cycles, res0_out, res_out);
+        c->bc_timer.commit();   // (mg_outer's norm reads have passed the scatter)
+        return rc;
+    }
     if (c->step_spec && !c->dist) {
         Level &L = c->lv[0];
         std::swap(L.rhs, L.rhs_alt);
@@ -2664,6 +2828,12 @@ extern "C" int mgx_get_tuning(const char *key, long *value) {
         double us = 0, bytes = 0;
         mgxdiag::last_pass(&us, &bytes);
         *value = key[6] == 'u' ? (long)us : (long)bytes;
+        return MGX_OK;
+    }
+    // (read-only: the device microseconds of the calling thread's last ring
+    // write, mgx_set_boundary* now or consumed by a step)
+    if (!strcmp(key, "boundary_us")) {
+        *value = (long)mgxbc::last_us();
         return MGX_OK;
     }
     if (!strcmp(key, "vgen")) {

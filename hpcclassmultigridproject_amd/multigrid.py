@@ -252,6 +252,57 @@ class Multigrid:
         check(lib().mgx_source_info(self._h, C.byref(a), C.byref(s)))
         return bool(a.value), s.value
 
+    # -- time-dependent Dirichlet data (mgx_set_boundary)
+    _WHEN = {"now": _lib.BC_NOW, "next": _lib.BC_NEXT_STEP}
+
+    def set_boundary(self, g, when="now"):
+        """Replace the Dirichlet ring of the finest u (mgx_set_boundary).  g:
+        4(N+1) float64, flat or (4, N+1) -- u(0,:), u(N,:), u(:,0), u(:,N); the
+        corners are the rows' (entries 0 and N of the two column sides are
+        ignored) -- a numpy array or a torch tensor on the solver's device.
+        when="now": the ring is overwritten at once, every other bit of u and
+        the right-hand side stay.  when="next": the solver keeps a copy and the
+        next step() / step_ex() is rhs(); set_boundary(g, "now"); mg_outer()
+        bit for bit -- the Crank-Nicolson step from the old ring to the new
+        one; g=None cancels it.  Every kind of solver takes it; RCCL ranks
+        must all pass the same values."""
+        if when not in self._WHEN:
+            raise _lib.MGXError(_lib.MGX_E_ARG, "set_boundary: when must be 'now' or 'next'")
+        w = self._WHEN[when]
+        cnt = 4 * (self.N + 1)
+        if g is None:
+            check(lib().mgx_set_boundary(self._h, None, w))
+        elif isinstance(g, np.ndarray):
+            if g.size != cnt:
+                raise ValueError(f"g must hold {cnt} doubles")
+            check(lib().mgx_set_boundary(self._h, _np_ptr(g), w))
+        else:
+            if g.numel() != cnt:
+                raise ValueError(f"g must hold {cnt} doubles")
+            check(lib().mgx_set_boundary_device(self._h, _lib.device_ptr(g, cnt, "g"), w))
+
+    def get_boundary(self, out=None):
+        """The ring of the finest u (mgx_get_boundary) -> a (4, N+1) array, the
+        corner entries of the column sides filled with the corner values.  out:
+        a numpy array, or a device tensor the kernel writes directly.
+        Single-GPU and local-parts solvers."""
+        cnt = 4 * (self.N + 1)
+        if out is not None and not isinstance(out, np.ndarray):
+            check(lib().mgx_get_boundary_device(self._h, _lib.device_ptr(out, cnt, "out")))
+            return out
+        out = np.empty((4, self.N + 1), dtype=np.float64) if out is None else out
+        if out.size != cnt:
+            raise ValueError(f"out must hold {cnt} doubles")
+        check(lib().mgx_get_boundary(self._h, _np_ptr(out)))
+        return out
+
+    def boundary_pending(self):
+        """1 while a ring set with when="next" waits for the next step, else 0
+        (mgx_boundary_info)."""
+        p = C.c_int()
+        check(lib().mgx_boundary_info(self._h, C.byref(p)))
+        return p.value
+
     def velocity_factored(self):
         """mgx_velocity_factored: bit 0 = the finest level keeps velocity
         factors, bit l = level l generates its velocity from them."""

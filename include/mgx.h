@@ -330,7 +330,7 @@ int mgx_get_tuning(const char *key, long *value);
  * xsmooth.hip, concatenated in that order -- the key the committed PMC
  * profiles are stamped with) and of every product source (those + ctx.h,
  * plan.h, sepvel.h, mgx.hip, dist.hip, vfactor.h, vfactor.hip, source.h,
- * source.hip, diag.h, diag.hip, include/mgx.h). */
+ * source.hip, diag.h, diag.hip, boundary.h, boundary.hip, include/mgx.h). */
 const char *mgx_build_id(void);
 const char *mgx_build_sources_id(void);
 
@@ -650,6 +650,75 @@ int mgx_sample_rows(mgx_ctx *ctx, int part, int field, long stride, double *out,
 /* (Read-only, mgx_get_tuning, beside "vfactor_us": "stats_us" / "stats_bytes"
  * = the device microseconds -- HIP events around the reduction launches only
  * -- and the compulsory bytes of the calling thread's last statistics call.) */
+
+/* ---- Time-dependent Dirichlet data: the ring of u on a live context ---------
+ * The boundary values of the finest u are data: every pass reads them and
+ * carries them from its input to its output, none computes them.  These calls
+ * replace them without moving u off the device (csrc/boundary.hip, part of
+ * mgx_build_sources_id).
+ *
+ * g holds 4(N+1) doubles, side-major:
+ *     g[0*(N+1)+j] = u(0,j)    g[2*(N+1)+i] = u(i,0)
+ *     g[1*(N+1)+j] = u(N,j)    g[3*(N+1)+i] = u(i,N)
+ * The four corners belong to the two row sides: entries 0 and N of sides 2
+ * and 3 are ignored on input, and mgx_get_boundary fills them with the corner
+ * values.
+ *
+ * when = MGX_BC_NOW: the ring of the finest u is overwritten now; every other
+ * bit of u and the whole right-hand side stay as they are.  What was formed
+ * with the old ring is dropped, as by mgx_set_source: a speculative
+ * pre-smoothed u, a pending next step, the cross pass's bookkeeping, and a
+ * deferred coarsest solve; a packed pre-smoothed u is expanded first.
+ * Captured sub-cycles stay (they hold no finest-level value).  g == NULL is
+ * MGX_E_ARG.
+ *
+ * when = MGX_BC_NEXT_STEP: the context copies g (its own device copy,
+ * allocated by the first call) and marks it pending.  The next mgx_step or
+ * mgx_step_ex consumes it: that step is, bit for bit and cycle count for cycle
+ * count,
+ *     mgx_rhs(ctx);  mgx_set_boundary(ctx, g, MGX_BC_NOW);  mgx_mg_outer(ctx, ...)
+ * -- Crank-Nicolson's rhs = B u^n with the old ring g^n, then A u^(n+1) = rhs
+ * with the new ring g^(n+1), mg_outer taking its initial norm after the ring
+ * is written.  That step runs the plain schedule (no rhs + norm + pre-smoothing
+ * fusion) and prepares no next step; steps with nothing pending run exactly
+ * what they ran before.  Setting a ring drops a prepared next step at once.
+ * g == NULL cancels a pending ring.  A pending ring survives
+ * mgx_set_velocity* and mgx_set_source*; mgx_upload*, mgx_upload_rows and
+ * mgx_destroy cancel it.
+ *
+ * Every kind of context takes mgx_set_boundary*: local parts and RCCL ranks
+ * write the two column entries of every row they hold (ghost rows included)
+ * and rows 0 / N where they hold them; with every level replicated each
+ * sub-context is written.  No communication: every RCCL rank passes the same
+ * values, as with mgx_set_source_separable.  mgx_get_boundary* serves
+ * single-GPU and local-parts contexts; an RCCL rank returns MGX_E_ARG (it
+ * would need communication: use mgx_download_rows or mgx_sample_rows).
+ * mgx_boundary_info: *pending = 1 while a MGX_BC_NEXT_STEP ring waits.
+ *
+ * Every call here checks its arguments before any device call and reports
+ * MGX_E_ARG with a message that starts with its own name.  A context that
+ * never calls them, and mgx_timestepper[_ex], launch what they launched
+ * before.
+ * Measured on one MI355X (DESIGN.md section 11, N=16384, L=9, fma, three
+ * cycles per step): a step with a device ring set every step takes 12.9 ms
+ * against 8.0 ms for the plain step -- 4.9 ms for the plain schedule (its own
+ * rhs pass and initial norm, no step fusion, no prepared next step); the ring
+ * write itself is 7 microseconds.  mgx_download_device, a ring edit and
+ * mgx_upload_device before every step, the only route before, take 28.5 ms
+ * per step.  The read-only tuning key "boundary_us" (mgx_get_tuning) gives the
+ * device microseconds of the calling thread's last ring write (HIP events
+ * around its launches). */
+#define MGX_BC_NOW 0
+#define MGX_BC_NEXT_STEP 1
+int mgx_set_boundary(mgx_ctx *ctx, const double *g, int when);          /* host g   */
+int mgx_set_boundary_device(mgx_ctx *ctx, const double *g, int when);   /* device g */
+int mgx_get_boundary(mgx_ctx *ctx, double *g);                          /* host out   */
+int mgx_get_boundary_device(mgx_ctx *ctx, double *g);                   /* device out */
+int mgx_boundary_info(mgx_ctx *ctx, int *pending);
+/* The gs.h-style raw op: device pointers, u in the reference layout ((n+1)^2
+ * row-major), any n >= 1, null stream: the ring of u = g (layout above), the
+ * interior untouched. */
+int mgx_write_boundary(double *u, long n, const double *g);
 
 #ifdef __cplusplus
 }
