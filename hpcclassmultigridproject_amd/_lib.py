@@ -146,6 +146,8 @@ _SIGS = {
     "mgx_get_boundary_device": (_I, [_vp, _vp]),
     "mgx_boundary_info": (_I, [_vp, C.POINTER(_I)]),
     "mgx_write_boundary": (_I, [_vp, _L, _vp]),
+    "mgx_set_time_step": (_I, [_vp, _D, _D]),
+    "mgx_time_step_info": (_I, [_vp, _dp, _dp]),
     "mgx_build_id": (C.c_char_p, []),
     "mgx_build_sources_id": (C.c_char_p, []),
 }

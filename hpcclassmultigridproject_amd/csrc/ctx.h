@@ -61,7 +61,12 @@ struct Level {
     // v2 equal the generator's entries from the finest factors (checked at
     // upload, stencil.h vg_col)
     bool vgen = false;
-    mgx::Coef coef{};
+    // coef: the solve side A of the context's step (k = kA, mgx_ctx::kA), the
+    // context's fp_mode; coef_rhs: what the compute_rhs kernels take, which
+    // read the B side of a Coef alone (rr, nu, h, drhs) -- make_coef(kB) in the
+    // bitwise form, or coef itself while kA == kB (Crank-Nicolson: every launch
+    // gets the arguments it got before mgx_set_time_step existed)
+    mgx::Coef coef{}, coef_rhs{};
     double M() const { return double(n + 1) * double(n + 1); }
     // compulsory bytes of v1 + v2 of this level (the zero rows cost no HBM)
     double Mv() const { return double(std::min<long>(n + 1, vz)) * double(n + 1); }
@@ -86,6 +91,15 @@ struct mgx_ctx {
     long N = 0;
     int L = 0;
     double dt = 0, nu = 0;
+    // mgx_set_time_step: the theta-scheme (I + theta dt L) u' = (I - (1 - theta)
+    // dt L) u + dt f is the reference's two operators with k = kA on the solve
+    // side and k = kB on the right-hand side (C doubles, each product rounded:
+    // every translation unit is built without contraction).  theta = 0.5 gives
+    // kA == kB == dt exactly; two_op() is the schedules' branch test.
+    double theta = 0.5;
+    double kA() const { return (2.0 * theta) * dt; }
+    double kB() const { return (2.0 * (1.0 - theta)) * dt; }
+    bool two_op() const { return kA() != kB(); }
     mgx_options opt{};
     std::vector<mgxi::Level> lv;
     double *partials = nullptr;   // norm partial sums
@@ -239,6 +253,17 @@ int set_source_sep_ctx(mgx_ctx *c, int terms, const double *a, const double *b,
 // are null; who: the C entry point, for the message
 int copy_source_factors(double **da, double **db, long n, long pitch, int terms, const double *a,
                         const double *b, hipMemcpyKind kind, hipStream_t s, const char *who);
+// mgx_set_time_step on one context's own state (mgx.hip): dt, theta, every
+// level's coef / coef_rhs, and everything formed with the old coefficients
+// dropped -- drop_source_state's list, a deferred coarsest solve, the captured
+// sub-cycles (they hold Coef as kernel arguments).  The caller has expanded a
+// packed u_pre (op_expand, with the old coefficients) where one can exist.
+int retime_ctx(mgx_ctx *c, double dt, double theta);
+// the two Coefs of a level of spacing h for the context's dt and theta
+void step_coefs(const mgx_ctx *c, double h, mgx::Coef *coef, mgx::Coef *coef_rhs);
+// ... and on a partitioned context (dist.hip): every part's PLevel and every
+// replicated sub-context; no communication
+int dist_set_time_step(mgx_ctx *c, double dt, double theta);
 // tuning key "source_sv" (mgx.hip): the source pass reads the finest level's
 // velocity factors, where the context keeps them, instead of the 2-D v1 / v2
 extern long g_source_sv;

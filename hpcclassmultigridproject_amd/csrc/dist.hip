@@ -36,6 +36,7 @@
 #include "ctx.h"
 #include "plan.h"
 #include "source.h"
+#include "tstep.h"
 
 namespace mgxi {
 
@@ -126,7 +127,7 @@ struct PLevel {
     // level 0 of a row-block upload: the columns whose entries are the row
     // factors of v1 / v2 (sepvel.h j*), or -1
     long js1 = -1, js2 = -1;
-    mgx::Coef coef{};
+    mgx::Coef coef{}, coef_rhs{};   // Level::coef / coef_rhs
     int nxt() const { return cur == 0 ? 1 : 0; }
     // field pointer offset so that F(a) + r*pitch is global row r
     double *F(double *a) const { return a - (long)lo * pitch; }
@@ -256,7 +257,7 @@ static int build_dist(mgx_ctx *c, int world, const std::vector<int> &ranks) {
             PLevel L;
             L.n = c->N >> l;
             L.pitch = mgx::tower_pitch(L.n);
-            L.coef = mgx::make_coef(c->dt, c->nu, h, c->opt.fp_mode == MGX_FP_FMA);
+            step_coefs(c, h, &L.coef, &L.coef_rhs);   // (the context's dt and theta)
             alloc_rows(c->N, l, world, r, &L.ra, &L.rb, &L.lo, &L.hi);
             const bool third = l == 0 && L.n >= kCrossMinN;
             double **bufs[6] = {&L.u[0], &L.u[1], &L.rhs, &L.v1, &L.v2, &L.u[2]};
@@ -1033,7 +1034,7 @@ static mgxsrc::SrcArgs source_args(mgx_ctx *c, Part &p, bool norm, double *cbyte
     A.cf = c->dt * c->src_scale;
     A.n = L.n;
     A.pitch = L.pitch;
-    A.c = L.coef;
+    A.c = L.coef_rhs;   // (== coef while kA == kB)
     A.ra = L.ra;
     A.rb = L.rb;
     const bool sv = g_source_sv != 0 && L.sa1 && L.sb1 && L.sa2 && L.sb2;
@@ -1072,7 +1073,7 @@ int dist_rhs(mgx_ctx *c) {
             continue;
         }
         CHK(launch(c, MGX_K_RHS, 0, 32.0 * L.Mown(), [&] {
-            mgx::launch_rhs(L.F(L.rhs), L.U(), L.F(L.v1), L.F(L.v2), L.n, L.pitch, L.coef,
+            mgx::launch_rhs(L.F(L.rhs), L.U(), L.F(L.v1), L.F(L.v2), L.n, L.pitch, L.coef_rhs,
                             c->stream, L.ra, L.rb);
         }));
     }
@@ -1093,6 +1094,15 @@ int dist_rhs_norm(mgx_ctx *c, double *res0) {
     CHK(xchg(c, 0, kU));
     for (auto &p : d->parts) {
         PLevel &L = p.lv[0];
+        if (c->two_op()) {   // theta != 1/2: the two-operator pass (csrc/tstep.hip)
+            double cb = 0;
+            const mgxsrc::SrcArgs A = source_args(c, p, true, &cb);   // (or no source)
+            const bool field = A.f && !A.terms;
+            cb = ((A.sa1 ? 16.0 : 32.0) + (field ? 8.0 : 0.0)) * L.Mown();
+            CHK(launch(c, MGX_K_RHS, 0, (field ? 88.0 : 80.0) * L.Mown(), cb,
+                       [&] { mgxts::launch_rhs_norm2(A, L.coef, c->stream); }));
+            continue;
+        }
         if (L.has_source()) {
             double cb = 0;
             const mgxsrc::SrcArgs A = source_args(c, p, true, &cb);
@@ -1247,6 +1257,31 @@ int dist_set_source_sep(mgx_ctx *c, int terms, const double *a, const double *b,
     for (auto &p : d->parts) p.lv[0].src_terms = terms;
     c->src_terms = terms;
     c->src_active = true;
+    return MGX_OK;
+}
+// mgx_set_time_step on a partitioned context: every part's coefficients and
+// every replicated sub-context, the speculative states dropped as in
+// dist_boundary_now.  No communication: RCCL ranks pass the same values.
+int dist_set_time_step(mgx_ctx *c, double dt, double theta) {
+    Dist *d = c->dist;
+    HIPCHK(hipSetDevice(c->device));
+    CHK(settle(c));
+    for (auto &p : d->parts) {
+        if (!p.lv.empty()) {
+            p.lv[0].spec = -1;
+            p.lv[0].xin = -1;
+        }
+        if (p.sub) {
+            if (d->la == 0) {   // the sub-context holds the finest level: a packed u_pre
+                CHK(materialize(p.sub, 0));
+                CHK(op_expand(p.sub));
+            }
+            CHK(retime_ctx(p.sub, dt, theta));
+        }
+    }
+    CHK(retime_ctx(c, dt, theta));
+    for (auto &p : d->parts)
+        for (PLevel &L : p.lv) step_coefs(c, L.coef.h, &L.coef, &L.coef_rhs);
     return MGX_OK;
 }
 void dist_set_source_scale(mgx_ctx *c, double s) {

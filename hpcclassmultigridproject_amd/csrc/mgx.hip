@@ -21,6 +21,7 @@
 #include "diag.h"
 #include "sepvel.h"
 #include "source.h"
+#include "tstep.h"
 #include "vfactor.h"
 
 namespace mgxi {
@@ -891,7 +892,7 @@ static mgxsrc::SrcArgs source_args(mgx_ctx *c, bool norm, double *cbytes) {
     A.cf = c->dt * c->src_scale;
     A.n = L.n;
     A.pitch = L.pitch;
-    A.c = L.coef;
+    A.c = L.coef_rhs;   // (== coef while kA == kB: the norm instance needs that)
     const bool sv = g_source_sv != 0 && L.sa1 && L.sb1 && L.sa2 && L.sb2;
     if (sv) {
         A.sa1 = L.sa1;
@@ -919,7 +920,7 @@ int op_rhs(mgx_ctx *c) {
                       [&] { mgxsrc::launch_rhs_source(A, c->stream); });
     }
     return launch(c, MGX_K_RHS, 0, 32.0 * L.M(), [&] {
-        mgx::launch_rhs(L.rhs, L.U(), L.v1, L.v2, L.n, L.pitch, L.coef, c->stream);
+        mgx::launch_rhs(L.rhs, L.U(), L.v1, L.v2, L.n, L.pitch, L.coef_rhs, c->stream);
     });
 }
 
@@ -940,6 +941,23 @@ static int op_rhs_norm(mgx_ctx *c, double *res0) {
         mgx::launch_rhs_norm(L.rhs, L.U(), L.v1, L.v2, L.n, L.pitch, L.coef, c->partials,
                              c->dscal, c->stream);
     }));
+    return read_norm(c, res0);
+}
+
+// The same for a step whose two sides differ (mgx_ctx::two_op, theta != 1/2):
+// rhs = B(kB) u (+ the source term) and the norm of rhs - A(kA) u in one pass
+// (csrc/tstep.hip) -- the fused kernels above form both from one Coef.
+static int op_rhs_norm2(mgx_ctx *c, double *res0) {
+    drop_spec(c);
+    CHK(materialize(c, 0));
+    Level &L = c->lv[0];
+    double cb = 0;
+    const mgxsrc::SrcArgs A = source_args(c, true, &cb);   // (f and terms unset: no source)
+    const bool field = A.f && !A.terms;
+    // u, rhs (+ f of a field source) (+ v1, v2 without factors)
+    cb = ((A.sa1 ? 16.0 : 32.0) + (field ? 8.0 : 0.0)) * L.M();
+    CHK(launch(c, MGX_K_RHS, 0, (field ? 40.0 : 32.0) * L.M() + 48.0 * L.M(), cb,
+               [&] { mgxts::launch_rhs_norm2(A, L.coef, c->stream); }));
     return read_norm(c, res0);
 }
 
@@ -1392,6 +1410,7 @@ int mgxi::create_ctx(mgx_ctx **out, long n, int maxlvl, double dt, double nu,
         L.n = n >> l;
         L.pitch = mgx::tower_pitch(L.n);
         L.coef = mgx::make_coef(dt, nu, h, o.fp_mode == MGX_FP_FMA);
+        L.coef_rhs = L.coef;   // theta = 1/2 until mgx_set_time_step
         h = 2 * h;
         const size_t bytes = sizeof(double) * L.pitch * (L.n + 1);
         double **bufs[5] = {&L.u[0], &L.u[1], &L.rhs, &L.v1, &L.v2};
@@ -2145,6 +2164,51 @@ int mgx_write_boundary(double *u, long n, const double *g) {
     return check_launch("mgx_write_boundary");
 }
 
+}  // extern "C"
+
+// ---- per-step dt and theta (include/mgx.h, csrc/tstep.hip)
+void mgxi::step_coefs(const mgx_ctx *c, double h, mgx::Coef *coef, mgx::Coef *coef_rhs) {
+    *coef = mgx::make_coef(c->kA(), c->nu, h, c->opt.fp_mode == MGX_FP_FMA);
+    *coef_rhs = c->two_op() ? mgx::make_coef(c->kB(), c->nu, h) : *coef;
+}
+// Everything formed with the old coefficients goes: what mgx_set_boundary
+// drops, and the captured sub-cycles -- unlike a ring, the coefficients are
+// kernel arguments of every node of a graph.
+int mgxi::retime_ctx(mgx_ctx *c, double dt, double theta) {
+    drop_source_state(c);
+    c->cf_level = -1;
+    c->cf_reps = 0;
+    // (a replay may still be running: free_ctx drains the stream first too)
+    if (!c->graphs.empty()) HIPCHK(hipStreamSynchronize(c->stream));
+    free_graphs(c);
+    c->dt = dt;
+    c->theta = theta;
+    for (Level &L : c->lv) step_coefs(c, L.coef.h, &L.coef, &L.coef_rhs);
+    return MGX_OK;
+}
+
+extern "C" {
+
+int mgx_set_time_step(mgx_ctx *c, double dt, double theta) {
+    if (!c) return fail(MGX_E_ARG, "mgx_set_time_step: null ctx");
+    if (!std::isfinite(dt) || !(dt > 0))
+        return fail(MGX_E_ARG, "mgx_set_time_step: dt must be finite and > 0");
+    if (!std::isfinite(theta) || !(theta > 0) || !(theta <= 1))
+        return fail(MGX_E_ARG, "mgx_set_time_step: theta must satisfy 0 < theta <= 1");
+    HIPCHK(hipSetDevice(c->device));
+    if (c->dist) return dist_set_time_step(c, dt, theta);
+    // a packed u_pre is expanded with the operator that packed it
+    CHK(materialize(c, 0));
+    CHK(op_expand(c));
+    return retime_ctx(c, dt, theta);
+}
+int mgx_time_step_info(mgx_ctx *c, double *dt, double *theta) {
+    if (!c) return fail(MGX_E_ARG, "mgx_time_step_info: null ctx");
+    if (dt) *dt = c->dt;
+    if (theta) *theta = c->theta;
+    return MGX_OK;
+}
+
 static int no_dist(mgx_ctx *c, const char *what) {
     return fail(MGX_E_ARG, std::string(what) + ": per-level ops are not available on a "
                                                "partitioned context (use vcycle/mg_outer/step)");
@@ -2254,15 +2318,18 @@ static int step_impl(mgx_ctx *c, double tol, int *cycles, bool prepare_next,
         c->step_spec = false;   // lv[0].spec and lv[1]'s rhs stay: the first cycle's
     } else if (c->dist) {
         CHK(dist_rhs_norm(c, &res0));
+    } else if (c->two_op()) {
+        CHK(op_rhs_norm2(c, &res0));
     } else if (!c->has_source() && step_fusable(c)) {
         CHK(op_rhs_norm_pre(c, &res0));
     } else {
         CHK(op_rhs_norm(c, &res0));
     }
     // (a source: both fused forms make the rhs inside kernels that know none --
-    // k_wsmooth's kModeRhsNorm above, the cross pass's step mode here)
-    c->step_next =
-        prepare_next && g_step_cross != 0 && !c->dist && !c->has_source() && step_rhs_alt(c);
+    // k_wsmooth's kModeRhsNorm above, the cross pass's step mode here; theta !=
+    // 1/2: both form the rhs and smooth with one Coef)
+    c->step_next = prepare_next && g_step_cross != 0 && !c->dist && !c->has_source() &&
+                   !c->two_op() && step_rhs_alt(c);
     const int rc = op_mg_outer(c, tol, cycles, res0_out, res_out, &res0);
     c->step_next = false;
     return rc;

@@ -50,6 +50,9 @@ struct SrcArgs {
     int ra = 0, rb = -1;   // output rows [ra, rb) (rb < 0: the whole level), as launch_rhs
 };
 void launch_rhs_source(const SrcArgs &a, hipStream_t s);
+// the grid and rows per group of a norm instance over `rows` interior rows:
+// launch_residual_norm's (shared with tstep.hip)
+void res_grid(long n, long rows, dim3 &g, int &R);
 
 // reference layout (pitch n+1, one point per lane), the gs.h-style raw op
 void launch_raw_rhs_source(double *rhs, const double *u, const double *v1, const double *v2,

@@ -185,16 +185,6 @@ __global__ __launch_bounds__(256) void k_raw_rhs_source_sep(double *rhs, const d
     }
 }
 
-// kernels.hip's res_grid: the grid of every k_res_march launch (the norm
-// instance must cut the rows exactly as launch_residual_norm does)
-void res_grid(long n, long rows, dim3 &g, int &R) {
-    const unsigned strips = cdiv(n + 1, 512);
-    rows = std::max<long>(rows, 1);
-    const long want = std::max<long>(1, 4096 / (long)strips);
-    R = (int)std::max<long>(8, (rows + want - 1) / want);
-    g = dim3(strips, cdiv(rows, R));
-}
-
 template <bool NORM, bool SV, int SF>
 void launch_inst(const SrcArgs &a, dim3 g, int R, int f, int e, hipStream_t s) {
     MGX_LAUNCH((k_rhs_source<NORM, SV, SF>), g, dim3(256), s, a.u, a.v1, a.v2, a.sa1, a.sb1, a.sa2,
@@ -213,6 +203,16 @@ void launch_form(const SrcArgs &a, dim3 g, int R, int f, int e, hipStream_t s) {
 }
 
 }  // namespace
+
+// kernels.hip's res_grid: the grid of every k_res_march launch (the norm
+// instance must cut the rows exactly as launch_residual_norm does)
+void res_grid(long n, long rows, dim3 &g, int &R) {
+    const unsigned strips = cdiv(n + 1, 512);
+    rows = std::max<long>(rows, 1);
+    const long want = std::max<long>(1, 4096 / (long)strips);
+    R = (int)std::max<long>(8, (rows + want - 1) / want);
+    g = dim3(strips, cdiv(rows, R));
+}
 
 void launch_rhs_source(const SrcArgs &a, hipStream_t s) {
     int ra = a.ra, rb = a.rb;

@@ -92,6 +92,7 @@ class Multigrid:
                  coarse_tol=1e-5, coarse_maxit=1000, max_cycle=50,
                  world=1, rank=0, unique_id=None, local_parts=0, fp_mode=_lib.FP_BITWISE):
         self.N, self.maxlvl, self.dt, self.nu = N, maxlvl, dt, nu
+        self.theta = 0.5   # Crank-Nicolson until set_time_step()
         self.opt = default_options(nsmooth=nsmooth, shape=shape, tower_mode=tower_mode,
                                    device=device, smoother=smoother, fuse=fuse,
                                    coarse_tol=coarse_tol,
@@ -302,6 +303,28 @@ class Multigrid:
         p = C.c_int()
         check(lib().mgx_boundary_info(self._h, C.byref(p)))
         return p.value
+
+    # -- per-step dt and theta (mgx_set_time_step)
+    def set_time_step(self, dt=None, theta=None):
+        """The time step and the scheme of every later step (mgx_set_time_step):
+        (I + theta dt L) u' = (I - (1 - theta) dt L) u + dt f.  None keeps the
+        current value.  theta=0.5 is Crank-Nicolson (the solver's schedule as
+        before, bit for bit with the dt of the constructor), theta=1 implicit
+        Euler.  u, the right-hand side, the velocity, a source and a pending
+        ring stay; what was formed with the old coefficients is dropped.
+        self.dt and self.theta follow, so cfl() reports the new number.  RCCL
+        ranks must all pass the same values."""
+        cur_dt, cur_theta = self.time_step()
+        dt = cur_dt if dt is None else float(dt)
+        theta = cur_theta if theta is None else float(theta)
+        check(lib().mgx_set_time_step(self._h, dt, theta))
+        self.dt, self.theta = dt, theta
+
+    def time_step(self):
+        """-> (dt, theta) (mgx_time_step_info)."""
+        dt, th = C.c_double(), C.c_double()
+        check(lib().mgx_time_step_info(self._h, C.byref(dt), C.byref(th)))
+        return dt.value, th.value
 
     def velocity_factored(self):
         """mgx_velocity_factored: bit 0 = the finest level keeps velocity

@@ -330,7 +330,8 @@ int mgx_get_tuning(const char *key, long *value);
  * xsmooth.hip, concatenated in that order -- the key the committed PMC
  * profiles are stamped with) and of every product source (those + ctx.h,
  * plan.h, sepvel.h, mgx.hip, dist.hip, vfactor.h, vfactor.hip, source.h,
- * source.hip, diag.h, diag.hip, boundary.h, boundary.hip, include/mgx.h). */
+ * source.hip, diag.h, diag.hip, boundary.h, boundary.hip, tstep.h, tstep.hip,
+ * include/mgx.h). */
 const char *mgx_build_id(void);
 const char *mgx_build_sources_id(void);
 
@@ -719,6 +720,64 @@ int mgx_boundary_info(mgx_ctx *ctx, int *pending);
  * row-major), any n >= 1, null stream: the ring of u = g (layout above), the
  * interior untouched. */
 int mgx_write_boundary(double *u, long n, const double *g);
+
+/* ---- Per-step dt and theta on a live context ---------------------------------
+ * mgx_create fixes dt, and every step is Crank-Nicolson.  mgx_set_time_step
+ * changes both for every later call, without touching the towers: a step
+ * becomes the theta-scheme
+ *     (I + theta dt L) u^(n+1) = (I - (1 - theta) dt L) u^n + dt f,
+ * theta = 1/2 Crank-Nicolson, theta = 1 implicit Euler (a few of which, at
+ * dt/2, damp the ringing Crank-Nicolson shows on non-smooth data: Rannacher
+ * start-up).  dt is finite and > 0, theta finite with 0 < theta <= 1; anything
+ * else is MGX_E_ARG, reported before any device call with a message that
+ * starts with the function's name.  A context that never calls it has theta =
+ * 0.5 and the dt of mgx_create.
+ *
+ * Meaning, bit for bit.  With the C doubles
+ *     kA = (2.0 * theta) * dt      kB = (2.0 * (1.0 - theta)) * dt
+ * (each product rounded, no contraction), from the call on
+ *   - every finest-level compute_rhs of the context (mgx_rhs, the start of
+ *     mgx_step) is the reference's compute_rhs with k = kB;
+ *   - everything that applies or inverts A on any level -- mgx_gs,
+ *     mgx_residual_norm, mgx_restrict, mgx_vcycle, mgx_mg_outer,
+ *     mgx_run_cycles, the coarsest solve -- is the reference's with k = kA.
+ * At theta = 0.5, kA == kB == dt exactly: mgx_set_time_step(ctx, dt of
+ * mgx_create, 0.5) changes no bit of anything that follows.  The source weight
+ * stays c = fl(dt * s) with the new dt (not kA or kB).  fp_mode fma contracts
+ * the kA operator exactly as it contracts today's; the right-hand side and
+ * mg_outer's initial norm stay in the reference's term order.  The residual
+ * norms mgx_step_ex returns are within 1e-11 relative of the exact norm of the
+ * stored fields, as everywhere.
+ *
+ * The call drops what was formed with the old coefficients -- what
+ * mgx_set_boundary(MGX_BC_NOW) drops (a speculative pre-smoothed u, a packed
+ * one expanded first; a prepared next step; the cross pass's bookkeeping; a
+ * deferred coarsest solve) and the captured sub-cycles of "graph_level", whose
+ * nodes hold the coefficients as kernel arguments.  It keeps u, the right-hand
+ * side, the velocity tower and its factors, a source and its scale, and a
+ * pending ring; the setting belongs to the context and survives mgx_upload*
+ * and mgx_set_velocity*.
+ *
+ * Schedule.  While kA == kB (as doubles) every schedule runs what it ran
+ * before, launch for launch (a step right after the call only lacks the
+ * prepared next step it dropped).  Otherwise mgx_step starts with one pass of
+ * its own (csrc/tstep.hip, part of mgx_build_sources_id; profile kind
+ * MGX_K_RHS): rhs = B(kB) u, plus the source term of a field or separable
+ * source, and in the same march the norm of rhs - A(kA) u -- bitwise mgx_rhs
+ * followed by mgx_residual_norm(ctx, 0).  Its algorithmic bytes are those of
+ * the fused rhs + norm pass, its compulsory bytes 16 / 32 per point with /
+ * without velocity factors, plus 8 with a field source.  "step_fuse" and
+ * "step_cross" are off for such a context: their kernels form the right-hand
+ * side and smooth with one set of coefficients (the same reason as for a
+ * source).  The cross-cycle pass inside mg_outer stays on.
+ *
+ * Every kind of context takes the call: local parts and RCCL ranks set every
+ * part and every replicated sub-context.  No communication: RCCL ranks pass the
+ * same values, as with mgx_set_source_separable.  mgx_timestepper[_ex] and the
+ * raw gs.h ops are untouched.
+ * mgx_time_step_info: the current dt and theta (either pointer may be NULL). */
+int mgx_set_time_step(mgx_ctx *ctx, double dt, double theta);
+int mgx_time_step_info(mgx_ctx *ctx, double *dt, double *theta);
 
 #ifdef __cplusplus
 }
