@@ -5,9 +5,9 @@ Drop-in for the hot path of soniareilly/HPCClassMultigridProject: the V-cycle
 kernels in libmgx.so behind the C ABI of include/mgx.h.
 """
 from . import gs
-from ._lib import MGXError, Options, default_options, lib
+from ._lib import MGXError, Options, bdf2_coefficients, default_options, lib
 from .multigrid import (Multigrid, default_maxlvl, init_problem, init_problem_rows,
                         timestepper, write_uT)
 
-__all__ = ["gs", "MGXError", "Options", "default_options", "lib", "Multigrid",
-           "default_maxlvl", "init_problem", "init_problem_rows", "timestepper", "write_uT"]
+__all__ = ["gs", "MGXError", "Options", "bdf2_coefficients", "default_options", "lib",
+           "Multigrid", "default_maxlvl", "init_problem", "init_problem_rows", "timestepper", "write_uT"]

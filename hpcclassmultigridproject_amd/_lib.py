@@ -148,6 +148,12 @@ _SIGS = {
     "mgx_write_boundary": (_I, [_vp, _L, _vp]),
     "mgx_set_time_step": (_I, [_vp, _D, _D]),
     "mgx_time_step_info": (_I, [_vp, _dp, _dp]),
+    "mgx_bdf2_coefficients": (_I, [_D, _D, _dp, _dp, _dp, _dp]),
+    "mgx_set_history": (_I, [_vp, _I]),
+    "mgx_history_info": (_I, [_vp, C.POINTER(_I), C.POINTER(_I), _dp, _dp]),
+    "mgx_step_bdf2": (_I, [_vp, _D, C.POINTER(_I), _dp, _dp]),
+    "mgx_rollback": (_I, [_vp]),
+    "mgx_compute_rhs_bdf2": (_I, [_vp, _vp, _vp, _L, _D, _D, _vp, _D]),
     "mgx_build_id": (C.c_char_p, []),
     "mgx_build_sources_id": (C.c_char_p, []),
 }
@@ -242,6 +248,28 @@ def compute_rhs_source_separable(rhs, u, n, v1, v2, k, nu, h, a, b, c):
     ptrs = [device_ptr(x, (n + 1) * (n + 1)) for x in (rhs, u, v1, v2)]
     check(lib().mgx_compute_rhs_source_separable(ptrs[0], ptrs[1], n, ptrs[2], ptrs[3], k, nu, h,
                                                  terms, a.data_ptr(), b.data_ptr(), c))
+
+
+def bdf2_coefficients(dt, dt_prev):
+    """mgx_bdf2_coefficients -> (g, b0, b1, kA): the doubles of a variable-step
+    BDF2 step dt after a step dt_prev (host only): w = dt/dt_prev, g = (1+w) /
+    (1+2w), b0 = (1+w)^2 / (1+2w), b1 = w^2 / (1+2w), kA = (2g) dt, each
+    operation rounded."""
+    g, b0, b1, kA = C.c_double(), C.c_double(), C.c_double(), C.c_double()
+    check(lib().mgx_bdf2_coefficients(float(dt), float(dt_prev), C.byref(g), C.byref(b0),
+                                      C.byref(b1), C.byref(kA)))
+    return g.value, b0.value, b1.value, kA.value
+
+
+def compute_rhs_bdf2(rhs, u, h, n, b0, b1, f=None, c=0.0):
+    """mgx_compute_rhs_bdf2: rhs = fl(fl(b0*u) - fl(b1*h)) (then fl(that +
+    fl(c*f)) where f is given) on the interior; nothing else is written.
+    Device tensors (float64, contiguous, (n+1)^2 entries, reference layout) or
+    raw device pointers; null stream."""
+    cnt = (n + 1) * (n + 1)
+    check(lib().mgx_compute_rhs_bdf2(device_ptr(rhs, cnt, "rhs"), device_ptr(u, cnt, "u"),
+                                     device_ptr(h, cnt, "h"), n, b0, b1,
+                                     device_ptr(f, cnt, "f"), c))
 
 
 def device_ptr(x, count, what="tensor"):

@@ -100,6 +100,19 @@ struct mgx_ctx {
     double kA() const { return (2.0 * theta) * dt; }
     double kB() const { return (2.0 * (1.0 - theta)) * dt; }
     bool two_op() const { return kA() != kB(); }
+    // mgx_step_bdf2 (csrc/bdf.h): k_bdf != 0 = every level's coef is built with
+    // that k instead of kA() (the BDF2 solve side, A = I + g dt L) until the next
+    // mgx_rhs, mgx_step* or mgx_set_time_step puts the theta-scheme's back
+    double k_bdf = 0;
+    double k_solve() const { return k_bdf != 0 ? k_bdf : kA(); }
+    // mgx_set_history: hist = one more finest-level array in the layout of
+    // lv[0].u, u^n while u becomes u^(n+1) (a partitioned context keeps one in
+    // every part, or in every sub-context where all levels are replicated, and
+    // the flags here); hist_valid: it holds the u a step started from, and
+    // hist_dt is that step's dt
+    double *hist = nullptr;
+    bool hist_on = false, hist_valid = false;
+    double hist_dt = 0;
     mgx_options opt{};
     std::vector<mgxi::Level> lv;
     double *partials = nullptr;   // norm partial sums
@@ -258,12 +271,31 @@ int copy_source_factors(double **da, double **db, long n, long pitch, int terms,
 // dropped -- drop_source_state's list, a deferred coarsest solve, the captured
 // sub-cycles (they hold Coef as kernel arguments).  The caller has expanded a
 // packed u_pre (op_expand, with the old coefficients) where one can exist.
-int retime_ctx(mgx_ctx *c, double dt, double theta);
+// k_bdf: mgx_ctx::k_bdf from the call on (0: the theta-scheme's solve side)
+int retime_ctx(mgx_ctx *c, double dt, double theta, double k_bdf = 0.0);
 // the two Coefs of a level of spacing h for the context's dt and theta
 void step_coefs(const mgx_ctx *c, double h, mgx::Coef *coef, mgx::Coef *coef_rhs);
 // ... and on a partitioned context (dist.hip): every part's PLevel and every
 // replicated sub-context; no communication
-int dist_set_time_step(mgx_ctx *c, double dt, double theta);
+int dist_set_time_step(mgx_ctx *c, double dt, double theta, double k_bdf = 0.0);
+// mgx_set_history and what goes with it (csrc/bdf.h) on one context's own
+// state (mgx.hip).  hist_alloc_ctx: MGX_E_HIP with a message when there is no
+// room; hist_snapshot_ctx: hist = what mgx_download would return now;
+// op_rhs_norm_bdf: the BDF2 pass (rhs, h <- u, the norm against coef) with the
+// source weight cf; hist_restore_ctx: u = hist, everything formed with the old
+// u dropped (boundary_prepare_ctx).  None synchronises but the norm read.
+int hist_alloc_ctx(mgx_ctx *c, const char *who);
+void hist_free_ctx(mgx_ctx *c);
+int hist_snapshot_ctx(mgx_ctx *c);
+int op_rhs_norm_bdf(mgx_ctx *c, double b0, double b1, double cf, double *res0);
+int hist_restore_ctx(mgx_ctx *c);
+// ... and on a partitioned context (dist.hip): every part's owned rows, or
+// every sub-context where all levels are replicated.  dist_rhs_norm_bdf mirrors
+// dist_rhs_norm's two-operator branch: the u ghosts before, the rhs ghosts after
+int dist_set_history(mgx_ctx *c, int on, const char *who);
+int dist_snapshot(mgx_ctx *c);
+int dist_rhs_norm_bdf(mgx_ctx *c, double b0, double b1, double cf, double *res0);
+int dist_rollback(mgx_ctx *c);
 // tuning key "source_sv" (mgx.hip): the source pass reads the finest level's
 // velocity factors, where the context keeps them, instead of the 2-D v1 / v2
 extern long g_source_sv;

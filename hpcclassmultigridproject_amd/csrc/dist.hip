@@ -37,6 +37,7 @@
 #include "plan.h"
 #include "source.h"
 #include "tstep.h"
+#include "bdf.h"
 
 namespace mgxi {
 
@@ -119,6 +120,9 @@ struct PLevel {
     double *src_a = nullptr, *src_b = nullptr;
     int src_terms = 0;
     bool has_source() const { return src != nullptr || src_terms > 0; }
+    // level 0: the history of mgx_set_history (mgx_ctx::hist), the layout of a u
+    // buffer -- its owned rows [ra, rb) are the part's share of u^n -- or null
+    double *hist = nullptr;
     // level 0: exact velocity factors (sepvel.h) indexed by GLOBAL row / column
     // (full-length arrays, this block's rows filled), or null
     double *sa1 = nullptr, *sb1 = nullptr, *sa2 = nullptr, *sb2 = nullptr;
@@ -204,6 +208,7 @@ void dist_free(mgx_ctx *c) {
             (void)hipFree(L.src);
             (void)hipFree(L.src_a);
             (void)hipFree(L.src_b);
+            (void)hipFree(L.hist);
             for (double *f : {L.sa1, L.sb1, L.sa2, L.sb2}) (void)hipFree(f);
         }
         if (p.sub) free_ctx(p.sub);
@@ -1262,7 +1267,7 @@ int dist_set_source_sep(mgx_ctx *c, int terms, const double *a, const double *b,
 // mgx_set_time_step on a partitioned context: every part's coefficients and
 // every replicated sub-context, the speculative states dropped as in
 // dist_boundary_now.  No communication: RCCL ranks pass the same values.
-int dist_set_time_step(mgx_ctx *c, double dt, double theta) {
+int dist_set_time_step(mgx_ctx *c, double dt, double theta, double k_bdf) {
     Dist *d = c->dist;
     HIPCHK(hipSetDevice(c->device));
     CHK(settle(c));
@@ -1276,13 +1281,133 @@ int dist_set_time_step(mgx_ctx *c, double dt, double theta) {
                 CHK(materialize(p.sub, 0));
                 CHK(op_expand(p.sub));
             }
-            CHK(retime_ctx(p.sub, dt, theta));
+            CHK(retime_ctx(p.sub, dt, theta, k_bdf));
         }
     }
-    CHK(retime_ctx(c, dt, theta));
+    CHK(retime_ctx(c, dt, theta, k_bdf));
     for (auto &p : d->parts)
         for (PLevel &L : p.lv) step_coefs(c, L.coef.h, &L.coef, &L.coef_rhs);
     return MGX_OK;
+}
+// mgx_set_history on a partitioned context: one array per part, the size of a
+// u buffer of its level 0 (all parts or none); with every level replicated each
+// sub-context keeps its own.  The flags stay in c (mgx.hip).
+int dist_set_history(mgx_ctx *c, int on, const char *who) {
+    Dist *d = c->dist;
+    HIPCHK(hipSetDevice(c->device));
+    CHK(settle(c));
+    auto free_all = [&] {
+        (void)hipStreamSynchronize(c->stream);   // a pass may still read it
+        for (auto &p : d->parts) {
+            if (d->la == 0) {
+                hist_free_ctx(p.sub);
+            } else {
+                (void)hipFree(p.lv[0].hist);
+                p.lv[0].hist = nullptr;
+            }
+        }
+    };
+    if (!on) {
+        free_all();
+        return MGX_OK;
+    }
+    int rc = MGX_OK;
+    for (auto &p : d->parts) {
+        if (rc != MGX_OK) break;
+        if (d->la == 0) {
+            rc = hist_alloc_ctx(p.sub, who);
+            continue;
+        }
+        PLevel &L = p.lv[0];
+        if (L.hist) continue;
+        const hipError_t e = hipMalloc(&L.hist, L.bytes());
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            L.hist = nullptr;
+            rc = fail(MGX_E_HIP, std::string(who) + ": no room for the part's history (one "
+                                                    "finest-level block): " + hipGetErrorString(e));
+        }
+    }
+    if (rc != MGX_OK) free_all();   // all parts or none
+    return rc;
+}
+// h = what mgx_download would return: every part's owned rows (whole pitched
+// rows, contiguous), or every sub-context's u
+int dist_snapshot(mgx_ctx *c) {
+    Dist *d = c->dist;
+    HIPCHK(hipSetDevice(c->device));
+    CHK(settle(c));
+    for (auto &p : d->parts) {
+        if (d->la == 0) {
+            CHK(hist_snapshot_ctx(p.sub));
+            continue;
+        }
+        PLevel &L = p.lv[0];
+        const long off = (long)L.ra * L.pitch;
+        HIPCHK(hipMemcpyAsync(L.F(L.hist) + off, L.U() + off,
+                              sizeof(double) * (size_t)(L.rb - L.ra) * L.pitch,
+                              hipMemcpyDeviceToDevice, c->stream));
+    }
+    return MGX_OK;
+}
+// The first pass of a BDF2 step per part (csrc/bdf.hip; mgx.hip:
+// op_rhs_norm_bdf), the shape of dist_rhs_norm's two-operator branch: u ghosts
+// once (the norm's stencil reads them), the rhs ghosts after.  The right-hand
+// side and the store over h are pointwise on the owned rows: no exchange more.
+int dist_rhs_norm_bdf(mgx_ctx *c, double b0, double b1, double cf, double *res0) {
+    Dist *d = c->dist;
+    HIPCHK(hipSetDevice(c->device));
+    CHK(settle(c));
+    dist_drop_spec(c);
+    if (d->la == 0) {
+        for (auto &p : d->parts) CHK(op_rhs_norm_bdf(p.sub, b0, b1, cf, res0));
+        return MGX_OK;
+    }
+    CHK(xchg(c, 0, kU));
+    for (auto &p : d->parts) {
+        PLevel &L = p.lv[0];
+        double cb = 0;
+        mgxsrc::SrcArgs A = source_args(c, p, true, &cb);   // (or no source)
+        A.c = L.coef;
+        A.cf = cf;
+        const bool field = A.f && !A.terms;
+        cb = ((A.sa1 ? 32.0 : 48.0) + (field ? 8.0 : 0.0)) * L.Mown();
+        CHK(launch(c, MGX_K_RHS, 0, (field ? 96.0 : 88.0) * L.Mown(), cb, [&] {
+            mgxbdf::launch_rhs_norm_bdf(A, L.F(L.hist), b0, b1, c->stream);
+        }));
+    }
+    CHK(xchg(c, 0, kRhs));
+    return reduce_norm(c, res0);
+}
+// mgx_rollback on a partitioned context: every part's owned rows of u from its
+// history, the ghost rows from their owners again, and the speculative states
+// dropped as in dist_boundary_now.
+int dist_rollback(mgx_ctx *c) {
+    Dist *d = c->dist;
+    HIPCHK(hipSetDevice(c->device));
+    CHK(settle(c));
+    for (auto &p : d->parts) {
+        if (!p.lv.empty()) {
+            p.lv[0].spec = -1;
+            p.lv[0].xin = -1;
+        }
+        if (d->la == 0) {
+            CHK(hist_restore_ctx(p.sub));
+            continue;
+        }
+        drop_source_state(p.sub);
+        p.sub->cf_level = -1;
+        p.sub->cf_reps = 0;
+        PLevel &L = p.lv[0];
+        const long off = (long)L.ra * L.pitch;
+        HIPCHK(hipMemcpyAsync(L.U() + off, L.F(L.hist) + off,
+                              sizeof(double) * (size_t)(L.rb - L.ra) * L.pitch,
+                              hipMemcpyDeviceToDevice, c->stream));
+    }
+    drop_source_state(c);
+    if (d->la == 0) return MGX_OK;
+    d->early_buf[0] = -1;   // (an early exchange carried the rejected step's rows)
+    return xchg(c, 0, kU);
 }
 void dist_set_source_scale(mgx_ctx *c, double s) {
     for (auto &p : c->dist->parts) {
@@ -2107,6 +2232,7 @@ int mgx_upload_rows(mgx_ctx *c, const double *const *u0, const double *const *v1
                     const double *const *v2) {
     if (!c || !c->dist) return fail(MGX_E_ARG, "mgx_upload_rows: not a partitioned context");
     c->bc_pending = false;   // a pending ring belongs to the old u (mgx_upload)
+    c->hist_valid = false;   // ... and so does a history
     return dist_upload_rows_impl(c, u0, v1, v2);
 }
 

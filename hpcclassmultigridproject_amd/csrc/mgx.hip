@@ -22,6 +22,7 @@
 #include "sepvel.h"
 #include "source.h"
 #include "tstep.h"
+#include "bdf.h"
 #include "vfactor.h"
 
 namespace mgxi {
@@ -961,6 +962,62 @@ static int op_rhs_norm2(mgx_ctx *c, double *res0) {
     return read_norm(c, res0);
 }
 
+// The first pass of a BDF2 step (csrc/bdf.hip): rhs = b0 u - b1 h (+ cf f), u
+// stored over h on the whole array, and the norm of rhs - A u with the level's
+// coef (the caller has built it with kA) in one march.
+int op_rhs_norm_bdf(mgx_ctx *c, double b0, double b1, double cf, double *res0) {
+    drop_spec(c);
+    CHK(materialize(c, 0));
+    CHK(op_expand(c));   // (as mgx_download: h becomes what it would return)
+    Level &L = c->lv[0];
+    double cb = 0;
+    mgxsrc::SrcArgs A = source_args(c, true, &cb);   // (f and terms unset: no source)
+    A.c = L.coef;
+    A.cf = cf;
+    const bool field = A.f && !A.terms;
+    // u and h in, h and rhs out (+ f of a field source) (+ v1, v2 without factors)
+    cb = ((A.sa1 ? 32.0 : 48.0) + (field ? 8.0 : 0.0)) * L.M();
+    CHK(launch(c, MGX_K_RHS, 0, (field ? 96.0 : 88.0) * L.M(), cb,
+               [&] { mgxbdf::launch_rhs_norm_bdf(A, c->hist, b0, b1, c->stream); }));
+    return read_norm(c, res0);
+}
+
+// mgx_set_history on one context's own state
+int hist_alloc_ctx(mgx_ctx *c, const char *who) {
+    if (c->hist) return MGX_OK;
+    const Level &L = c->lv[0];
+    const size_t bytes = sizeof(double) * (size_t)(L.n + 1) * (size_t)L.pitch;
+    const hipError_t e = hipMalloc(&c->hist, bytes);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        c->hist = nullptr;
+        return fail(MGX_E_HIP, std::string(who) + ": no room for the history (one finest-level "
+                                                  "array): " + hipGetErrorString(e));
+    }
+    return MGX_OK;
+}
+void hist_free_ctx(mgx_ctx *c) {
+    if (!c->hist) return;
+    (void)hipStreamSynchronize(c->stream);   // a pass may still read it
+    (void)hipFree(c->hist);
+    c->hist = nullptr;
+}
+int hist_snapshot_ctx(mgx_ctx *c) {
+    CHK(materialize(c, 0));
+    CHK(op_expand(c));   // as mgx_download
+    const Level &L = c->lv[0];
+    const size_t bytes = sizeof(double) * (size_t)(L.n + 1) * (size_t)L.pitch;
+    HIPCHK(hipMemcpyAsync(c->hist, L.U(), bytes, hipMemcpyDeviceToDevice, c->stream));
+    return MGX_OK;
+}
+int hist_restore_ctx(mgx_ctx *c) {
+    CHK(boundary_prepare_ctx(c));
+    const Level &L = c->lv[0];
+    const size_t bytes = sizeof(double) * (size_t)(L.n + 1) * (size_t)L.pitch;
+    HIPCHK(hipMemcpyAsync(L.U(), c->hist, bytes, hipMemcpyDeviceToDevice, c->stream));
+    return MGX_OK;
+}
+
 // A time step's compute_rhs, mg_outer's initial norm AND the first cycle's
 // pre-smoothing + restriction in ONE pass over u, v1, v2 (k_wsmooth mode
 // kModeRhsNorm): u_pre goes to the free buffer and is left as the
@@ -1269,6 +1326,7 @@ void free_ctx(mgx_ctx *c) {
     (void)hipFree(c->src_b);
     (void)hipFree(c->diag);
     (void)hipFree(c->bc_buf);
+    (void)hipFree(c->hist);
     c->bc_timer.destroy();
     if (c->hscal) (void)hipHostFree(c->hscal);
     for (auto &r : c->pending) {
@@ -1771,11 +1829,13 @@ int mgx_compute_rhs_source(double *rhs, const double *u, long n, const double *v
 // every upload cancels it)
 int mgx_upload(mgx_ctx *c, const double *u0, const double *v1, const double *v2) {
     if (c) c->bc_pending = false;
+    if (c) c->hist_valid = false;   // (a history belongs to the old u too)
     if (c && c->dist) return dist_upload(c, u0, v1, v2, hipMemcpyHostToDevice);
     return upload_ctx(c, u0, v1, v2, hipMemcpyHostToDevice);
 }
 int mgx_upload_device(mgx_ctx *c, const double *u0, const double *v1, const double *v2) {
     if (c) c->bc_pending = false;
+    if (c) c->hist_valid = false;
     if (c && c->dist) return dist_upload(c, u0, v1, v2, hipMemcpyDeviceToDevice);
     return upload_ctx(c, u0, v1, v2, hipMemcpyDeviceToDevice);
 }
@@ -2168,13 +2228,15 @@ int mgx_write_boundary(double *u, long n, const double *g) {
 
 // ---- per-step dt and theta (include/mgx.h, csrc/tstep.hip)
 void mgxi::step_coefs(const mgx_ctx *c, double h, mgx::Coef *coef, mgx::Coef *coef_rhs) {
-    *coef = mgx::make_coef(c->kA(), c->nu, h, c->opt.fp_mode == MGX_FP_FMA);
-    *coef_rhs = c->two_op() ? mgx::make_coef(c->kB(), c->nu, h) : *coef;
+    *coef = mgx::make_coef(c->k_solve(), c->nu, h, c->opt.fp_mode == MGX_FP_FMA);
+    // (k_bdf set: a BDF2 step forms its own right-hand side; the theta-scheme's
+    // coefficients come back, k_bdf = 0, before anything reads coef_rhs)
+    *coef_rhs = c->two_op() || c->k_bdf != 0 ? mgx::make_coef(c->kB(), c->nu, h) : *coef;
 }
 // Everything formed with the old coefficients goes: what mgx_set_boundary
 // drops, and the captured sub-cycles -- unlike a ring, the coefficients are
 // kernel arguments of every node of a graph.
-int mgxi::retime_ctx(mgx_ctx *c, double dt, double theta) {
+int mgxi::retime_ctx(mgx_ctx *c, double dt, double theta, double k_bdf) {
     drop_source_state(c);
     c->cf_level = -1;
     c->cf_reps = 0;
@@ -2183,6 +2245,7 @@ int mgxi::retime_ctx(mgx_ctx *c, double dt, double theta) {
     free_graphs(c);
     c->dt = dt;
     c->theta = theta;
+    c->k_bdf = k_bdf;
     for (Level &L : c->lv) step_coefs(c, L.coef.h, &L.coef, &L.coef_rhs);
     return MGX_OK;
 }
@@ -2213,8 +2276,20 @@ static int no_dist(mgx_ctx *c, const char *what) {
     return fail(MGX_E_ARG, std::string(what) + ": per-level ops are not available on a "
                                                "partitioned context (use vcycle/mg_outer/step)");
 }
+// The solve side of every level with k = k_bdf (a BDF2 step's kA), or the
+// theta-scheme's again (0): mgx_set_time_step with the context's own dt and
+// theta -- the same drops, a packed u_pre expanded first with the operator
+// that packed it.
+static int set_solve_k(mgx_ctx *c, double k_bdf) {
+    HIPCHK(hipSetDevice(c->device));
+    if (c->dist) return dist_set_time_step(c, c->dt, c->theta, k_bdf);
+    CHK(materialize(c, 0));
+    CHK(op_expand(c));
+    return retime_ctx(c, c->dt, c->theta, k_bdf);
+}
 int mgx_rhs(mgx_ctx *c) {
     if (!c) return fail(MGX_E_ARG, "null ctx");
+    if (c->k_bdf != 0) CHK(set_solve_k(c, 0.0));   // after mgx_step_bdf2
     if (c->dist) return dist_rhs(c);
     return op_rhs(c);
 }
@@ -2297,6 +2372,12 @@ static int step_impl(mgx_ctx *c, double tol, int *cycles, bool prepare_next,
     // multigrid.cpp:168-170), with the first pre-smoothing where it fuses --
     // or already done by the previous step's last cross pass
     double res0 = 0;
+    if (c->k_bdf != 0) CHK(set_solve_k(c, 0.0));   // after mgx_step_bdf2
+    if (c->hist_on) {   // mgx_set_history: h = u^n, before a pending ring is written
+        CHK(c->dist ? dist_snapshot(c) : hist_snapshot_ctx(c));
+        c->hist_dt = c->dt;
+        c->hist_valid = true;
+    }
     if (c->bc_pending) {
         // a pending ring (mgx_set_boundary, MGX_BC_NEXT_STEP): the rhs with the
         // old ring, the new ring, then mg_outer with its own initial norm --
@@ -2327,9 +2408,10 @@ static int step_impl(mgx_ctx *c, double tol, int *cycles, bool prepare_next,
     }
     // (a source: both fused forms make the rhs inside kernels that know none --
     // k_wsmooth's kModeRhsNorm above, the cross pass's step mode here; theta !=
-    // 1/2: both form the rhs and smooth with one Coef)
+    // 1/2: both form the rhs and smooth with one Coef; a history: the next
+    // step may be a BDF2 one)
     c->step_next = prepare_next && g_step_cross != 0 && !c->dist && !c->has_source() &&
-                   !c->two_op() && step_rhs_alt(c);
+                   !c->two_op() && !c->hist_on && step_rhs_alt(c);
     const int rc = op_mg_outer(c, tol, cycles, res0_out, res_out, &res0);
     c->step_next = false;
     return rc;
@@ -2342,6 +2424,108 @@ int mgx_step_ex(mgx_ctx *c, double tol, int *cycles, double *res0, double *res) 
     if (!c) return fail(MGX_E_ARG, "mgx_step_ex: null ctx");
     return step_impl(c, tol, cycles, true, res0, res);
 }
+
+// ---- variable-step BDF2 on a device-resident history (include/mgx.h, csrc/bdf.hip)
+int mgx_bdf2_coefficients(double dt, double dt_prev, double *g, double *b0, double *b1,
+                          double *kA) {
+    if (!std::isfinite(dt) || !(dt > 0))
+        return fail(MGX_E_ARG, "mgx_bdf2_coefficients: dt must be finite and > 0");
+    if (!std::isfinite(dt_prev) || !(dt_prev > 0))
+        return fail(MGX_E_ARG, "mgx_bdf2_coefficients: dt_prev must be finite and > 0");
+    const mgxbdf::Coefs k = mgxbdf::coefficients(dt, dt_prev);
+    if (g) *g = k.g;
+    if (b0) *b0 = k.b0;
+    if (b1) *b1 = k.b1;
+    if (kA) *kA = k.kA;
+    return MGX_OK;
+}
+int mgx_set_history(mgx_ctx *c, int on) {
+    if (!c) return fail(MGX_E_ARG, "mgx_set_history: null ctx");
+    if (on != 0 && on != 1) return fail(MGX_E_ARG, "mgx_set_history: on must be 0 or 1");
+    if (on && c->hist_on) return MGX_OK;
+    if (!on && !c->hist_on) return MGX_OK;
+    HIPCHK(hipSetDevice(c->device));
+    if (on) {
+        // a prepared next step belongs to a schedule that a history turns off
+        if (c->dist)
+            CHK(dist_set_history(c, 1, "mgx_set_history"));
+        else
+            CHK(hist_alloc_ctx(c, "mgx_set_history"));
+        drop_step_spec(c);
+        c->hist_on = true;
+        c->hist_valid = false;
+        c->hist_dt = 0;
+        return MGX_OK;
+    }
+    if (c->dist)
+        CHK(dist_set_history(c, 0, "mgx_set_history"));
+    else
+        hist_free_ctx(c);
+    c->hist_on = false;
+    c->hist_valid = false;
+    c->hist_dt = 0;
+    return MGX_OK;
+}
+int mgx_history_info(mgx_ctx *c, int *on, int *valid, double *dt_prev, double *k_solve) {
+    if (!c) return fail(MGX_E_ARG, "mgx_history_info: null ctx");
+    if (on) *on = c->hist_on ? 1 : 0;
+    if (valid) *valid = c->hist_valid ? 1 : 0;
+    if (dt_prev) *dt_prev = c->hist_dt;
+    if (k_solve) *k_solve = c->k_solve();
+    return MGX_OK;
+}
+int mgx_step_bdf2(mgx_ctx *c, double tol, int *cycles, double *res0_out, double *res_out) {
+    if (!c) return fail(MGX_E_ARG, "mgx_step_bdf2: null ctx");
+    if (!c->hist_on)
+        return fail(MGX_E_ARG, "mgx_step_bdf2: the context has no history (mgx_set_history)");
+    if (!c->hist_valid)
+        return fail(MGX_E_ARG, "mgx_step_bdf2: the history is not valid: it holds no u^(n-1) "
+                               "(a theta-step, mgx_step, starts it)");
+    const mgxbdf::Coefs K = mgxbdf::coefficients(c->dt, c->hist_dt);
+    const double cf = (K.g * c->dt) * c->src_scale;
+    if (K.kA != c->k_solve()) CHK(set_solve_k(c, K.kA));
+    HIPCHK(hipSetDevice(c->device));
+    drop_step_spec(c);
+    // rhs, h <- u^n and mg_outer's initial norm in one pass
+    double res0 = 0;
+    if (c->dist)
+        CHK(dist_rhs_norm_bdf(c, K.b0, K.b1, cf, &res0));
+    else
+        CHK(op_rhs_norm_bdf(c, K.b0, K.b1, cf, &res0));
+    c->hist_dt = c->dt;
+    if (c->bc_pending) {
+        // a pending ring: written after the pass, and mg_outer takes its own
+        // initial norm, as step_impl orders it
+        c->bc_pending = false;
+        CHK(boundary_now(c, c->bc_buf));
+        const int rc = op_mg_outer(c, tol, cycles, res0_out, res_out);
+        c->bc_timer.commit();
+        return rc;
+    }
+    return op_mg_outer(c, tol, cycles, res0_out, res_out, &res0);
+}
+int mgx_rollback(mgx_ctx *c) {
+    if (!c) return fail(MGX_E_ARG, "mgx_rollback: null ctx");
+    if (!c->hist_on || !c->hist_valid)
+        return fail(MGX_E_ARG, "mgx_rollback: the context has no valid history (mgx_set_history, "
+                               "then a step)");
+    HIPCHK(hipSetDevice(c->device));
+    if (c->dist)
+        CHK(dist_rollback(c));
+    else
+        CHK(hist_restore_ctx(c));
+    c->hist_valid = false;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return MGX_OK;
+}
+int mgx_compute_rhs_bdf2(double *rhs, const double *u, const double *h, long n, double b0,
+                         double b1, const double *f, double c) {
+    if (!rhs || !u || !h) return fail(MGX_E_ARG, "mgx_compute_rhs_bdf2: null pointer");
+    if (n < 2) return fail(MGX_E_ARG, "mgx_compute_rhs_bdf2: n must be >= 2");
+    mgxbdf::launch_raw_rhs_bdf(rhs, u, h, n, b0, b1, f, c, nullptr);
+    return check_launch("mgx_compute_rhs_bdf2");
+}
+
 int mgx_run_cycles(mgx_ctx *c, int cycles, double *res) {
     if (!c || cycles < 0) return fail(MGX_E_ARG, "mgx_run_cycles: bad args");
     drop_step_spec(c);

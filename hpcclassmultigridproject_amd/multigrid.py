@@ -326,6 +326,42 @@ class Multigrid:
         check(lib().mgx_time_step_info(self._h, C.byref(dt), C.byref(th)))
         return dt.value, th.value
 
+    # -- variable-step BDF2 on a device-resident history (mgx_set_history)
+    def set_history(self, on=True):
+        """mgx_set_history: keep one more finest-level array h on the device
+        (one per part) that holds u^n while u becomes u^(n+1) -- what
+        step_bdf2() and rollback() need.  Every step() / step_ex() / step_bdf2()
+        then begins by making h what download() would return.  on=False frees
+        it.  Raises MGXError (MGX_E_HIP) where there is no room."""
+        check(lib().mgx_set_history(self._h, 1 if on else 0))
+
+    def history_info(self):
+        """-> dict(on, valid, dt_prev, k_solve) (mgx_history_info): valid = h
+        holds the u the last step started from, dt_prev = that step's dt,
+        k_solve = the k every solve-side call currently uses."""
+        on, valid = C.c_int(), C.c_int()
+        dtp, ks = C.c_double(), C.c_double()
+        check(lib().mgx_history_info(self._h, C.byref(on), C.byref(valid), C.byref(dtp),
+                                     C.byref(ks)))
+        return {"on": on.value, "valid": valid.value, "dt_prev": dtp.value,
+                "k_solve": ks.value}
+
+    def step_bdf2(self, tol=1e-6):
+        """One variable-step BDF2 step with the context's dt after the last
+        step's (mgx_step_bdf2) -> (cycles, res0, res).  Needs a valid history: a
+        theta-step (step()) starts it.  Zero-stability needs dt / dt_prev < 1 +
+        sqrt(2); nothing is refused."""
+        cyc, r0, r = C.c_int(), C.c_double(), C.c_double()
+        check(lib().mgx_step_bdf2(self._h, tol, C.byref(cyc), C.byref(r0), C.byref(r)),
+              allow=(_lib.MGX_E_NOCONV,))
+        return cyc.value, r0.value, r.value
+
+    def rollback(self):
+        """mgx_rollback: u becomes the u the last step started from (ring
+        included) and the history loses its validity -- the next step is a
+        theta-step: call step() next."""
+        check(lib().mgx_rollback(self._h))
+
     def velocity_factored(self):
         """mgx_velocity_factored: bit 0 = the finest level keeps velocity
         factors, bit l = level l generates its velocity from them."""

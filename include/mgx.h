@@ -331,7 +331,7 @@ int mgx_get_tuning(const char *key, long *value);
  * profiles are stamped with) and of every product source (those + ctx.h,
  * plan.h, sepvel.h, mgx.hip, dist.hip, vfactor.h, vfactor.hip, source.h,
  * source.hip, diag.h, diag.hip, boundary.h, boundary.hip, tstep.h, tstep.hip,
- * include/mgx.h). */
+ * bdf.h, bdf.hip, include/mgx.h). */
 const char *mgx_build_id(void);
 const char *mgx_build_sources_id(void);
 
@@ -778,6 +778,102 @@ int mgx_write_boundary(double *u, long n, const double *g);
  * mgx_time_step_info: the current dt and theta (either pointer may be NULL). */
 int mgx_set_time_step(mgx_ctx *ctx, double dt, double theta);
 int mgx_time_step_info(mgx_ctx *ctx, double *dt, double *theta);
+
+/* ---- Variable-step BDF2 steps on a device-resident history --------------------
+ * theta = 1/2 is second order but rings on non-smooth data; theta = 1 damps but
+ * is first order.  BDF2 is second order and L-stable, and with dt changing per
+ * step (mgx_set_time_step) it is the variable-step form, which needs u^(n-1).
+ * mgx_set_history(ctx, 1) gives the context one more finest-level array h (one
+ * per part of a partitioned context) that holds u^n while u becomes u^(n+1).
+ * The same array is the way back from a rejected step (mgx_rollback) without a
+ * download before every step.
+ *
+ * Meaning, bit for bit.  All C doubles, every operation rounded, nothing
+ * contracted in either fp_mode (mgx_bdf2_coefficients returns them; host only,
+ * any output pointer may be NULL; a non-finite or non-positive dt or dt_prev
+ * is MGX_E_ARG):
+ *     w  = dt / dt_prev        p = 1.0 + w        q = 1.0 + 2.0 * w
+ *     g  = p / q               b0 = (p * p) / q   b1 = (w * w) / q
+ *     kA = (2.0 * g) * dt      c  = (g * dt) * s        (s: mgx_set_source_scale)
+ * A BDF2 step is, on the interior (boundary entries of rhs untouched),
+ *     rhs(i,j) = fl( fl(b0*u(i,j)) - fl(b1*h(i,j)) )
+ *                [ then fl(that + fl(c*f(i,j))) with a source, f formed exactly
+ *                  as stated for mgx_set_source* above ]
+ * followed by mg_outer with the reference's solve operator at k = kA, that is
+ * A = I + g dt L.  Constant steps give g = 2/3, b0 = 4/3, b1 = 1/3.  dt is the
+ * context's (mgx_set_time_step), dt_prev the dt of the step that made the
+ * history.  Zero-stability needs w < 1 + sqrt(2); that is the caller's
+ * business and nothing is refused.
+ *
+ * mgx_set_history(ctx, on): on = 1 allocates h, all parts or none -- on failure
+ * MGX_E_HIP with a message, and the context stays without a history (N=65536
+ * on one GPU has no room); on a context that has one it is a no-op and keeps
+ * its validity.  on = 0 frees it.  A context that never calls it launches
+ * exactly what it launches without this section.
+ * mgx_history_info: whether a history is on, whether it is valid (holds u^n of
+ * a step), the dt of that step, and k_solve, the k every solve-side call of
+ * the context currently uses.  Any pointer may be NULL.
+ *
+ * While a history is on, every mgx_step, mgx_step_ex and mgx_step_bdf2 begins
+ * by making h equal to what mgx_download would return at that moment (u^n with
+ * ring and corners, before a pending ring is written), and sets dt_prev = dt,
+ * valid = 1.  mgx_step[_ex] gives, bit for bit and cycle for cycle, what it
+ * gives without a history (one device copy goes ahead of the step), but
+ * prepares no next step: "step_cross" is off while a history is on, for the
+ * reason a source turns it off -- the next step may be a BDF2 one.
+ *
+ * mgx_step_bdf2(ctx, tol, cycles, res0, res) (outputs may be NULL; returns
+ * MGX_E_NOCONV as mgx_step does): MGX_E_ARG before any device call, with a
+ * message that starts with the function's name, for a NULL ctx, a context
+ * without a history, and a history that is not valid (a theta-step starts
+ * it).  Where kA differs from k_solve it drops what mgx_set_time_step drops
+ * (a packed pre-smoothed u expanded first, with the operator that packed it)
+ * and rebuilds every level's coefficients.  Then ONE pass (csrc/bdf.hip, part
+ * of mgx_build_sources_id; profile kind MGX_K_RHS) stores rhs, stores u over h
+ * on the whole array and takes the norm of rhs - A(kA) u, bitwise what
+ * mgx_residual_norm(ctx, 0) returns right after; one launch plus the norm's
+ * final reduction, on a single GPU and per part.  A ring pending from
+ * MGX_BC_NEXT_STEP is written after the pass, and mg_outer then takes its own
+ * initial norm, as mgx_step orders it.  mg_outer runs with kA; no next step is
+ * prepared.  k_solve stays kA until the next mgx_rhs, mgx_step[_ex] or
+ * mgx_set_time_step, each of which re-establishes the theta-scheme's
+ * coefficients before anything else.
+ * Profile accounting of the pass: compulsory bytes 32 per finest point with
+ * velocity factors (u in, h in, h out, rhs out), 48 without, plus 8 with a
+ * field source; algorithmic bytes 88, plus 8 with a field source.  Measured at
+ * N=16384 (one MI355X, fma, velocity factors): the pass 1.51 ms against 4.16 ms
+ * for rhs + device copy + norm; a BDF2 step 11.4 ms, a theta = 1/2 step on the
+ * same context 10.9 ms, without a history 8.2 ms.
+ *
+ * Validity is cleared by mgx_upload*, mgx_upload_rows, mgx_rollback and
+ * mgx_set_history(ctx, 0); it is kept by mgx_set_velocity*, mgx_set_source*,
+ * mgx_set_boundary* and mgx_set_time_step -- keeping it across a dt change is
+ * the point.
+ *
+ * mgx_rollback(ctx): MGX_E_ARG without a valid history.  Otherwise u becomes h,
+ * ring included (a device copy), what mgx_set_boundary(MGX_BC_NOW) drops is
+ * dropped and valid is cleared: u^(n-1) is gone, so the next step is a
+ * theta-step.  From then on the context behaves, bit for bit, as a twin that
+ * was given u^n by mgx_upload with the same velocity, source and settings.
+ * The right-hand side is stale afterwards: call mgx_step next.
+ *
+ * Every kind of context takes all of this: local parts and RCCL ranks keep one
+ * h per part (the owned rows are the history; the pass is pointwise plus the
+ * norm the partitioned step already takes, so no exchange is added), and with
+ * every level replicated each sub-context keeps its own.  mgx_timestepper[_ex]
+ * is untouched.
+ *
+ * Raw op mgx_compute_rhs_bdf2: device pointers, reference layout, any n >= 2,
+ * null stream; f may be NULL.  The expression above on the interior of rhs;
+ * nothing else is written. */
+int mgx_bdf2_coefficients(double dt, double dt_prev, double *g, double *b0, double *b1,
+                          double *kA);
+int mgx_set_history(mgx_ctx *ctx, int on);
+int mgx_history_info(mgx_ctx *ctx, int *on, int *valid, double *dt_prev, double *k_solve);
+int mgx_step_bdf2(mgx_ctx *ctx, double tol, int *cycles, double *res0, double *res);
+int mgx_rollback(mgx_ctx *ctx);
+int mgx_compute_rhs_bdf2(double *rhs, const double *u, const double *h, long n, double b0,
+                         double b1, const double *f, double c);
 
 #ifdef __cplusplus
 }
