@@ -39,8 +39,8 @@ SEQ_STIFF = (t(1, .5), b(1), b(.5), b(1), t(.5, 1), b(.7))   # N=4096 only
 # set "next", or None -- two BDF2 steps and the theta-step in the middle
 RINGS = (None, 0, None, 1, None, 2, None, None)
 
-# Every (N, L, params, field, tower, fp modes, sequence, extra) that
-# tests/test_gpu_bdf.py runs against the checker; tests/test_bdf_fields.py holds
+# Every (N, L, params, field, tower, fp modes, sequence, extra[, nsmooth, fuse,
+# shape]) that tests/test_gpu_bdf.py runs against the checker; tests/test_bdf_fields.py holds
 # the margins on the checker alone.  tower 0 / 1: reference / correct; fp 0 / 1:
 # bitwise / fma; extra: the separable source of rings.source_factors, scale 1,
 # plus the rings RINGS.
@@ -54,12 +54,37 @@ CASES = [
     (4096, 7, "easy", "generic", 0, (0, 1), SEQ, False),
     (4096, 7, "easy", "rank1", 0, (1,), SEQ_R1, False),
     (4096, 7, "stiff", "generic", 0, (1,), SEQ_STIFF, False),
+    # other schedules (nsmooth, fuse, shape after the eight fields above; the
+    # defaults are 3, 3, 1): a W-cycle context whose coarsest level (n = 32) is
+    # solved inside the pair pass of the level above it -- theta-steps, BDF2
+    # steps, pending rings and a source in one run -- and a context whose
+    # smoothings are two passes of one sweep
+    (256, 4, "easy", "generic", 0, (0, 1), SEQ, True, 3, 3, 2),
+    (128, 3, "easy", "generic", 0, (0, 1), SEQ, False, 2, 1, 1),
 ]
-CASE_PARAMS = [(N, L, p, f, tw, fp, seq, ex)
-               for N, L, p, f, tw, fps, seq, ex in CASES for fp in fps]
-CASE_IDS = ["N%d-L%d-%s-%s-t%d-%s%s" % (N, L, p, f, tw, "bitwise" if fp == 0 else "fma",
-                                        "-source-rings" if ex else "")
-            for N, L, p, f, tw, fp, seq, ex in CASE_PARAMS]
+SCHEDULE = (3, 3, 1)   # nsmooth, fuse, shape of a case that names none
+
+
+def _expand(cases):
+    out = []
+    for c in cases:
+        N, L, p, f, tw, fps, seq, ex = c[:8]
+        for fp in fps:
+            out.append((N, L, p, f, tw, fp, seq, ex) + (tuple(c[8:]) or SCHEDULE))
+    return out
+
+
+def _id(N, L, p, f, tw, fp, seq, ex, nsmooth, fuse, shape):
+    sched = "" if (nsmooth, fuse, shape) == SCHEDULE else "-s%df%d-%s" % (
+        nsmooth, fuse, "W" if shape == 2 else "V")
+    return "N%d-L%d-%s-%s-t%d-%s%s%s" % (N, L, p, f, tw, "bitwise" if fp == 0 else "fma",
+                                         "-source-rings" if ex else "", sched)
+
+
+# (N, L, params, field, tower, fp, sequence, extra, nsmooth, fuse, shape)
+CASE_PARAMS = _expand(CASES)
+CASE_IDS = [_id(*c) for c in CASE_PARAMS]
+CASE_ARGS = "N,L,pname,name,tower,fp,seq,extra,nsmooth,fuse,shape"
 
 
 def coefs(dt, dt_prev):

@@ -22,9 +22,27 @@ NU = -4e-4
 # multi-cycle state (speculative pre-smoothing, predicted stores, step fusion)
 # is exercised.  dt = 3/N with nu = -2e-3 diverges in the checker: stay at or
 # below the stiff numbers.
+#
+# The schedule cases (tests/schedules.py) run three cycles before their
+# mg_outer, at N <= 2048, and need a contraction per cycle that is neither
+# "easy"'s (V-cycles, nsmooth 3: 2e-9, the rounding floor after two cycles) nor
+# "stiff"'s (which diverges below N = 2048, tests/test_fields.py).  "viscNN" is
+# the stiff time step with nu = -N.N / N, that is a diffusion number dt |nu| /
+# h^2 = N.N whatever the size (stiff at N=4096: 1.64); measured with the
+# checker on generic(), r_k / r_(k-1) at N = 128 .. 1024:
+#   visc16: V nsmooth 3 0.05, 2 0.15, 4 0.016; W nsmooth 1 0.2-0.3, 2 0.02
+#   visc07: V nsmooth 4 0.07-0.1;  W nsmooth 2 0.1, 3 0.02-0.04, 4 0.01
+#   visc06: W nsmooth 4 0.1-0.2 (at -0.5 / N every schedule diverges)
+# and "easy3" is dt = 1 / (3 N) with the reference's nu: V nsmooth 1 0.1-0.15.
 PARAMS = {
     "easy": (lambda N: 1.0 / (10 * N), NU),
     "stiff": (lambda N: 1.0 / N, NU),
+    "easy3": (lambda N: 1.0 / (3 * N), NU),
+    "easy5": (lambda N: 1.0 / (5 * N), NU),
+    "visc30": (lambda N: 1.0 / N, lambda N: -3.0 / N),
+    "visc16": (lambda N: 1.0 / N, lambda N: -1.6 / N),
+    "visc07": (lambda N: 1.0 / N, lambda N: -0.7 / N),
+    "visc06": (lambda N: 1.0 / N, lambda N: -0.6 / N),
 }
 
 
@@ -56,7 +74,7 @@ def make(field, N, seed=SEED):
 def params(name, N):
     """-> (dt, nu) of PARAMS[name] at size N."""
     dt, nu = PARAMS[name]
-    return dt(N), nu
+    return dt(N), (nu(N) if callable(nu) else nu)
 
 
 def _grid(N):
@@ -195,6 +213,7 @@ class CheckerRun:
     def __init__(self, O, u0, v1, v2, N, L, dt, nu, tower=0, nsmooth=3, shape=1, fp=0):
         self.O, self.N, self.L, self.dt, self.nu = O, N, L, dt, nu
         self.nsmooth, self.shape, self.fp = nsmooth, shape, fp
+        self.coarse_its = 0   # sweeps of every coarsest solve so far (or_mg_inner's count)
         self.t = O.Tower(u0, v1, v2, N, L, tower)
         self.v1, self.v2 = self.t._keep[1], self.t._keep[2]
 
@@ -220,8 +239,13 @@ class CheckerRun:
 
     def cycle(self):
         """One V / W cycle -> the residual norm after it."""
-        self.t.mg_inner(self.dt, self.nu, shape=self.shape, nsmooth=self.nsmooth)
+        self.mg_inner()
         return self.norm()
+
+    def mg_inner(self):
+        """One V / W cycle and nothing else (no residual, no norm)."""
+        self.coarse_its += self.t.mg_inner(self.dt, self.nu, shape=self.shape,
+                                           nsmooth=self.nsmooth)
 
     def mg_outer(self, tol, max_cycle=50):
         """-> (cycles, r0, [r_1 .. r_cycles])"""

@@ -67,12 +67,13 @@ def test_constant_step_coefficients():
                 assert b[1] / a[1] < 1 + np.sqrt(2.0)
 
 
-@pytest.mark.parametrize("N,L,pname,field,tower,fp,seq,extra", B.CASE_PARAMS, ids=B.CASE_IDS)
-def test_no_cycle_norm_sits_at_the_tolerance(checker, N, L, pname, field, tower, fp, seq, extra):
+@pytest.mark.parametrize(B.CASE_ARGS, B.CASE_PARAMS, ids=B.CASE_IDS)
+def test_no_cycle_norm_sits_at_the_tolerance(checker, N, L, pname, name, tower, fp, seq, extra,
+                                             nsmooth, fuse, shape):
     O = checker
     O.set_fp_mode(fp)
     dt, nu = F.params(pname, N)
-    run = F.CheckerRun(O, *F.make(field, N), N, L, dt, nu, tower, fp=fp)
+    run = F.CheckerRun(O, *F.make(name, N), N, L, dt, nu, tower, nsmooth, shape, fp)
     try:
         steps = B.checker_steps(run, dt, seq, B.TOL, B.T.source_field(N)[2] if extra else None,
                                 B.RINGS if extra else None, keep_u=False)

@@ -70,15 +70,16 @@ def check_margins(key, steps):
         assert F.margin(r0, norms, TOL) >= F.MARGIN, (key, r0, norms)
 
 
-def checker(O, N, L, pname, name, tower=REF, fp=BITWISE, seq=B.SEQ, extra=False):
+def checker(O, N, L, pname, name, tower=REF, fp=BITWISE, seq=B.SEQ, extra=False,
+            sched=B.SCHEDULE):
     """bdf.checker_steps of one case, cached for the module; the margins of its
     norms are asserted before anything is compared with it."""
-    key = (N, L, pname, name, tower, fp, seq, extra)
+    key = (N, L, pname, name, tower, fp, seq, extra, sched)
     if key not in _CHECKER:
         dt, nu = F.params(pname, N)
 
         def go():
-            run = F.CheckerRun(O, *field(name, N), N, L, dt, nu, tower, fp=fp)
+            run = F.CheckerRun(O, *field(name, N), N, L, dt, nu, tower, sched[0], sched[2], fp)
             try:
                 return B.checker_steps(run, dt, seq, TOL, T.source_field(N)[2] if extra else None,
                                        B.RINGS if extra else None)
@@ -89,12 +90,13 @@ def checker(O, N, L, pname, name, tower=REF, fp=BITWISE, seq=B.SEQ, extra=False)
     return _CHECKER[key]
 
 
-def solver(N, L, pname, name, tower=REF, fp=BITWISE, seq=B.SEQ, extra=False):
+def solver(N, L, pname, name, tower=REF, fp=BITWISE, seq=B.SEQ, extra=False, sched=B.SCHEDULE):
     """bdf.solver_steps of a fresh single-GPU context with a history, cached."""
-    key = (N, L, pname, name, tower, fp, seq, extra)
+    key = (N, L, pname, name, tower, fp, seq, extra, sched)
     if key not in _SOLVER:
         dt, nu = F.params(pname, N)
-        with Multigrid(N, L, dt, nu, tower_mode=tower, fp_mode=fp) as mg:
+        with Multigrid(N, L, dt, nu, nsmooth=sched[0], fuse=sched[1], shape=sched[2],
+                       tower_mode=tower, fp_mode=fp) as mg:
             mg.upload(*field(name, N))
             mg.set_history()
             if extra:
@@ -153,10 +155,12 @@ def knobs():
 
 
 # ---------------------------------------------------------------- 1. meaning
-@pytest.mark.parametrize("N,L,pname,name,tower,fp,seq,extra", B.CASE_PARAMS, ids=B.CASE_IDS)
-def test_steps_equal_the_checker(oracle_mod, N, L, pname, name, tower, fp, seq, extra):
-    want = checker(oracle_mod, N, L, pname, name, tower, fp, seq, extra)
-    got = solver(N, L, pname, name, tower, fp, seq, extra)
+@pytest.mark.parametrize(B.CASE_ARGS, B.CASE_PARAMS, ids=B.CASE_IDS)
+def test_steps_equal_the_checker(oracle_mod, N, L, pname, name, tower, fp, seq, extra, nsmooth,
+                                 fuse, shape):
+    sched = (nsmooth, fuse, shape)
+    want = checker(oracle_mod, N, L, pname, name, tower, fp, seq, extra, sched)
+    got = solver(N, L, pname, name, tower, fp, seq, extra, sched)
     against_checker(got, want, N, f"N={N} L={L} {pname} {name} tower={tower} fp={fp}")
 
 
@@ -569,3 +573,67 @@ def test_local_parts_reject_and_retry(oracle_mod, knobs, min_rows):
     with Multigrid(N, L, dt, nu, fp_mode=FMA) as one:
         want = go(one)
     same_steps(got, want, N, f"G={G} retry")
+
+
+# ---------------------------------------------------------------- 8. a W-cycle context
+W_N, W_L, W_SCHED = 256, 4, (3, 3, 2)   # bdf.CASES' W-cycle context: coarsest n = 32
+
+
+def w_rollback_checker(O, fp):
+    """(t(1, .5), b(1), b(2)) on the checker's W-cycle context, then the
+    checker restarted from the u^n of the last BDF2 step for an implicit Euler
+    step of half the size -> (steps, u^n, the retried step)."""
+    N, L = W_N, W_L
+    dt, nu = F.params("easy", N)
+    u0, v1, v2 = field("generic", N)
+    seq = (B.t(1, .5), B.b(1), B.b(2))
+
+    def go():
+        run = F.CheckerRun(O, u0, v1, v2, N, L, dt, nu, REF, W_SCHED[0], W_SCHED[2], fp)
+        try:
+            steps = B.checker_steps(run, dt, seq, TOL)
+        finally:
+            run.close()
+        un = steps[1][3]
+        run = F.CheckerRun(O, un, v1, v2, N, L, dt, nu, REF, W_SCHED[0], W_SCHED[2], fp)
+        try:
+            retry = T.checker_steps(run, dt, ((.5, 1.0),), TOL)
+        finally:
+            run.close()
+        return seq, steps, un, retry
+    return with_checker(O, fp, go)
+
+
+@pytest.mark.parametrize("graph_level", [0, 1])
+def test_w_cycle_rollback_then_a_theta_step(oracle_mod, knobs, graph_level):
+    """A W-cycle context (pair passes, the coarsest solve deferred into them)
+    takes a BDF2 step back and repeats it as an implicit Euler step of half the
+    size: rollback, set_time_step -- which drops a deferred coarsest solve and
+    every captured sub-cycle -- and the theta-step equal the checker restarted
+    from u^n.  graph_level 1: level 1's sub-cycle is captured during the
+    steps, and captured again after set_time_step."""
+    N, L = W_N, W_L
+    dt, nu = F.params("easy", N)
+    seq, steps, un, retry = w_rollback_checker(oracle_mod, FMA)
+    check_margins("W rollback", steps)
+    check_margins("W retry", retry)
+    knobs(graph_level=graph_level)
+    assert _lib.get_tuning("graph_level") == graph_level
+    c0 = _lib.get_tuning("graph_captures")
+    with Multigrid(N, L, dt, nu, nsmooth=W_SCHED[0], fuse=W_SCHED[1], shape=W_SCHED[2],
+                   fp_mode=FMA) as mg:
+        mg.upload(*field("generic", N))
+        mg.set_history()
+        got = B.solver_steps(mg, dt, seq, TOL)
+        against_checker(got, steps, N, "W-cycle context")
+        c1 = _lib.get_tuning("graph_captures")
+        mg.rollback()
+        bits_equal(mg.download(), un, N, "rollback of a BDF2 step of a W-cycle context")
+        mg.set_time_step(float(B.step_dt(dt, .5)), 1.0)
+        cyc, r0, r = mg.step_ex(TOL)
+        c2 = _lib.get_tuning("graph_captures")
+        against_checker([(cyc, r0, r, mg.download())], retry, N, "theta-step after rollback")
+    if graph_level:
+        assert c1 > c0 and c2 > c1, (c0, c1, c2)
+    else:
+        assert c0 == c1 == c2, (c0, c1, c2)

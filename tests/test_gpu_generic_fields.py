@@ -172,16 +172,21 @@ def dev(a):
 SMOOTHERS = [(0, 3), (0, 2), (0, 1), (1, 3), (2, 3)]   # tests/test_gpu_ops.py
 
 
-@pytest.fixture(params=[(2048, 1 << 30, 0), (2048, 0, 1), (0, 1 << 30, 0)],
+@pytest.fixture(params=[(2048, 1 << 30, 0, None), (2048, 0, 1, None), (0, 1 << 30, 0, 0)],
                 ids=["tile", "tile32xcd", "march"])
 def tile_mode(request):
     """tests/test_gpu_ops.py: small levels as 2-D LDS tiles (16-row; or 32-row
-    tiles in XCD order) or as the row march (N=512: strips of 112 columns,
-    rows on both sides of the unguarded margins)."""
-    keys = ("tile_max_n", "tile32_min_n", "tile_xcd")
+    tiles in XCD order) or as the row march -- tile_max_n = 0 and
+    march_tile_rows = 0, without which levels this short fall back to tiles
+    (smooth_as_tiles).  The march's strips are 116 columns wide for three
+    sweeps (WCfg::W; 124 for one, 112 with a residual stage): N=512 is five strips, the last group of four
+    part-empty, N=128 two strips and its level 1 (n = 64) narrower than one;
+    the level ops launch the guarded form over the whole level."""
+    keys = ("tile_max_n", "tile32_min_n", "tile_xcd", "march_tile_rows")
     old = [_lib.get_tuning(k) for k in keys]
     for k, v in zip(keys, request.param):
-        _lib.set_tuning(k, v)
+        if v is not None:
+            _lib.set_tuning(k, v)
     yield request.param[0]
     for k, v in zip(keys, old):
         _lib.set_tuning(k, v)
@@ -330,9 +335,16 @@ def test_cycles_vs_checker(oracle_mod, tower, fp):
     cycles_case(oracle_mod, "generic", 5, tower, fp)
 
 
-@pytest.mark.parametrize("kw", [dict(nsmooth=2), dict(shape=2)], ids=["nsmooth2", "W"])
-def test_cycles_vs_checker_other_schedules(oracle_mod, kw):
-    cycles_case(oracle_mod, "generic", 4, REF, FMA, **kw)
+@pytest.mark.parametrize("L,fp,kw", [(4, FMA, dict(nsmooth=2)), (4, FMA, dict(shape=2)),
+                                     (7, BITWISE, dict(shape=2)), (7, FMA, dict(shape=2))],
+                         ids=["nsmooth2", "W", "W-L7-bitwise", "W-L7-fma"])
+def test_cycles_vs_checker_other_schedules(oracle_mod, L, fp, kw):
+    """L=4: the coarsest level (n = 512) is solved by the host loop.  W-cycles
+    at L=7 (tests/schedules.py's N=4096 case): the coarsest n = 64 is solved in
+    LDS inside the pair pass of level 5, which restricts into the level's
+    second rhs; levels 2-5 run pair passes, level 1 marches, and level 0 takes
+    its two visits around the cross pass."""
+    cycles_case(oracle_mod, "generic", L, REF, fp, **kw)
 
 
 def test_cycles_vs_checker_zero_boundary(oracle_mod):

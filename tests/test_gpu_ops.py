@@ -101,16 +101,28 @@ def test_context_tower_matches_oracle(oracle_mod, tower_mode):
 SMOOTHERS = [(0, 3), (0, 2), (0, 1), (1, 3), (2, 3)]   # (smoother, sweeps fused per pass)
 
 
-@pytest.fixture(params=[(2048, 1 << 30, 0), (2048, 0, 1), (0, 1 << 30, 0)],
+@pytest.fixture(params=[(2048, 1 << 30, 0, None), (2048, 0, 1, None), (0, 1 << 30, 0, 0)],
                 ids=["tile", "tile32xcd", "march"])
 def tile_mode(request):
     """Small levels as 2-D LDS tiles (16-row; or 32-row tiles in XCD order) or
-    as the row march."""
+    as the row march.  The march sets march_tile_rows = 0 next to tile_max_n =
+    0: with the default 16 a level whose march would give the resident waves
+    fewer than 16 rows each (every N <= 512 here) runs as tiles all the same
+    (smooth_as_tiles, csrc/wsmooth.hip); with both 0 no tile branch is left.
+
+    N = 16 on the march is a level narrower than one strip (one strip of 116
+    columns, lanes 3 .. 11 active) and shorter than the unguarded margins
+    (WCfg::TOP = 24, BOT = 10 for three sweeps).  The level ops always launch
+    the guarded form over one region of all strips and rows (smooth_winst:
+    march_regions with split = false, so TOP and BOT are not used); it clamps
+    every load to rows [0, n] and columns [0, pitch - 2] (pitch = 32 >= n + 2)
+    and stores only on owned rows and active kept lanes, so the size stays."""
     from hpcclassmultigridproject_amd import _lib
-    keys = ("tile_max_n", "tile32_min_n", "tile_xcd")
+    keys = ("tile_max_n", "tile32_min_n", "tile_xcd", "march_tile_rows")
     old = [_lib.get_tuning(k) for k in keys]
     for k, v in zip(keys, request.param):
-        _lib.set_tuning(k, v)
+        if v is not None:
+            _lib.set_tuning(k, v)
     yield request.param[0]
     for k, v in zip(keys, old):
         _lib.set_tuning(k, v)

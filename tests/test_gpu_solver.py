@@ -30,13 +30,22 @@ def test_timestepper_bitwise_vs_reference(tag):
     assert np.array_equal(uT, g["uT"])
 
 
-@pytest.fixture(params=[2048, 0], ids=["tile", "march"])
+@pytest.fixture(params=[(2048, None), (0, 0)], ids=["tile", "march"])
 def tile_mode(request):
+    """Levels n <= 2048 as LDS tiles, or every level as the row march:
+    tile_max_n = 0 alone leaves the tile fallback of short levels in place
+    (march_tile_rows, default 16: every level of N <= 1024 here), so the march
+    also sets march_tile_rows = 0, after which smooth_as_tiles
+    (csrc/wsmooth.hip) has no tile branch left."""
     from hpcclassmultigridproject_amd import _lib
-    old = _lib.get_tuning("tile_max_n")
-    _lib.set_tuning("tile_max_n", request.param)
-    yield request.param
-    _lib.set_tuning("tile_max_n", old)
+    keys = ("tile_max_n", "march_tile_rows")
+    old = [_lib.get_tuning(k) for k in keys]
+    for k, v in zip(keys, request.param):
+        if v is not None:
+            _lib.set_tuning(k, v)
+    yield request.param[0]
+    for k, v in zip(keys, old):
+        _lib.set_tuning(k, v)
 
 
 @pytest.mark.parametrize("smoother,fuse", [(0, 3), (0, 2), (0, 1), (1, 3), (2, 3)])

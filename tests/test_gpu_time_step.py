@@ -63,15 +63,16 @@ def with_checker(O, fp, fn):
         O.set_threads(1)
 
 
-def checker(O, N, L, pname, name, tower=REF, fp=BITWISE, seq=T.SEQ_EASY, extra=False):
+def checker(O, N, L, pname, name, tower=REF, fp=BITWISE, seq=T.SEQ_EASY, extra=False,
+            sched=T.SCHEDULE):
     """tsteps.checker_steps of one case, cached for the module; the margins of
     its norms are asserted before anything is compared with it."""
-    key = (N, L, pname, name, tower, fp, seq, extra)
+    key = (N, L, pname, name, tower, fp, seq, extra, sched)
     if key not in _CHECKER:
         dt, nu = F.params(pname, N)
 
         def go():
-            run = F.CheckerRun(O, *field(name, N), N, L, dt, nu, tower, fp=fp)
+            run = F.CheckerRun(O, *field(name, N), N, L, dt, nu, tower, sched[0], sched[2], fp)
             try:
                 return T.checker_steps(run, dt, seq, TOL, T.source_field(N)[2] if extra else None,
                                        T.RINGS if extra else None)
@@ -85,12 +86,13 @@ def checker(O, N, L, pname, name, tower=REF, fp=BITWISE, seq=T.SEQ_EASY, extra=F
     return steps
 
 
-def solver(N, L, pname, name, tower=REF, fp=BITWISE, seq=T.SEQ_EASY, extra=False):
+def solver(N, L, pname, name, tower=REF, fp=BITWISE, seq=T.SEQ_EASY, extra=False, sched=T.SCHEDULE):
     """tsteps.solver_steps of a fresh single-GPU context, cached."""
-    key = (N, L, pname, name, tower, fp, seq, extra)
+    key = (N, L, pname, name, tower, fp, seq, extra, sched)
     if key not in _SOLVER:
         dt, nu = F.params(pname, N)
-        with Multigrid(N, L, dt, nu, tower_mode=tower, fp_mode=fp) as mg:
+        with Multigrid(N, L, dt, nu, nsmooth=sched[0], fuse=sched[1], shape=sched[2],
+                       tower_mode=tower, fp_mode=fp) as mg:
             mg.upload(*field(name, N))
             if extra:
                 a, b, _ = T.source_field(N)
@@ -148,10 +150,12 @@ def knobs():
 
 
 # ---------------------------------------------------------------- 1. meaning
-@pytest.mark.parametrize("N,L,pname,name,tower,fp,seq,extra", T.CASE_PARAMS, ids=T.CASE_IDS)
-def test_steps_equal_the_checker(oracle_mod, N, L, pname, name, tower, fp, seq, extra):
-    want = checker(oracle_mod, N, L, pname, name, tower, fp, seq, extra)
-    got = solver(N, L, pname, name, tower, fp, seq, extra)
+@pytest.mark.parametrize(T.CASE_ARGS, T.CASE_PARAMS, ids=T.CASE_IDS)
+def test_steps_equal_the_checker(oracle_mod, N, L, pname, name, tower, fp, seq, extra, nsmooth,
+                                 fuse, shape):
+    sched = (nsmooth, fuse, shape)
+    want = checker(oracle_mod, N, L, pname, name, tower, fp, seq, extra, sched)
+    got = solver(N, L, pname, name, tower, fp, seq, extra, sched)
     against_checker(got, want, N, f"N={N} L={L} {pname} {name} tower={tower} fp={fp}")
 
 
@@ -461,3 +465,46 @@ def test_rccl_world1_equals_single(oracle_mod):
         N, L, lambda dt, nu: Multigrid(N, L, dt, nu, fp_mode=FMA, world=1, rank=0, unique_id=uid),
         lambda mg: mg.upload(*field("generic", N)))
     same_steps(got, solver(N, L, "easy", "generic", fp=FMA), N, "rccl world 1")
+
+
+# ---------------------------------------------------------------- 8. a W-cycle context
+@pytest.mark.parametrize("graph_level", [0, 1])
+def test_w_cycle_set_velocity_between_steps(oracle_mod, knobs, graph_level):
+    """tsteps.CASES' W-cycle context (N=256, L=4: pair passes, the coarsest
+    solve deferred into them) takes a step, then set_velocity with the two
+    arrays swapped, then another step: the second equals a checker tower
+    rebuilt with that velocity from the downloaded u."""
+    O = oracle_mod
+    N, L, sched = 256, 4, (3, 3, 2)
+    dt, nu = F.params("easy", N)
+    u0, v1, v2 = field("generic", N)
+
+    def one_step(u, a, b):
+        def go():
+            run = F.CheckerRun(O, u, a, b, N, L, dt, nu, REF, sched[0], sched[2], FMA)
+            try:
+                return T.checker_steps(run, dt, ((1, .5),), TOL)
+            finally:
+                run.close()
+        steps = with_checker(O, FMA, go)
+        for cyc, r0, norms, _ in steps:
+            assert cyc < 50 and norms[-1] / r0 <= TOL, (cyc, r0, norms)
+            assert F.margin(r0, norms, TOL) >= F.MARGIN, (r0, norms)
+        return steps
+    knobs(graph_level=graph_level)
+    assert _lib.get_tuning("graph_level") == graph_level
+    c0 = _lib.get_tuning("graph_captures")
+    with Multigrid(N, L, dt, nu, nsmooth=sched[0], fuse=sched[1], shape=sched[2],
+                   fp_mode=FMA) as mg:
+        mg.upload(u0, v1, v2)
+        cyc, r0, r = mg.step_ex(TOL)
+        u1 = mg.download()
+        against_checker([(cyc, r0, r, u1)], one_step(u0, v1, v2), N, "first step")
+        mg.set_velocity(np.array(v2), np.array(v1))
+        want = one_step(u1, np.array(v2), np.array(v1))
+        cyc, r0, r = mg.step_ex(TOL)
+        against_checker([(cyc, r0, r, mg.download())], want, N, "step after set_velocity")
+    # (level 1's sub-cycle went through the graph path: a W-cycle enters it twice
+    # a cycle, from different states, and these steps take one cycle each)
+    c1 = _lib.get_tuning("graph_captures")
+    assert (c1 > c0) if graph_level else (c1 == c0), (c0, c1)

@@ -80,12 +80,13 @@ def test_the_loop_at_crank_nicolson_is_checker_step(checker, fp):
         b.close()
 
 
-@pytest.mark.parametrize("N,L,pname,field,tower,fp,seq,extra", T.CASE_PARAMS, ids=T.CASE_IDS)
-def test_no_cycle_norm_sits_at_the_tolerance(checker, N, L, pname, field, tower, fp, seq, extra):
+@pytest.mark.parametrize(T.CASE_ARGS, T.CASE_PARAMS, ids=T.CASE_IDS)
+def test_no_cycle_norm_sits_at_the_tolerance(checker, N, L, pname, name, tower, fp, seq, extra,
+                                             nsmooth, fuse, shape):
     O = checker
     O.set_fp_mode(fp)
     dt, nu = F.params(pname, N)
-    run = F.CheckerRun(O, *F.make(field, N), N, L, dt, nu, tower, fp=fp)
+    run = F.CheckerRun(O, *F.make(name, N), N, L, dt, nu, tower, nsmooth, shape, fp)
     try:
         steps = T.checker_steps(run, dt, seq, T.TOL, T.source_field(N)[2] if extra else None,
                                 T.RINGS if extra else None, keep_u=False)

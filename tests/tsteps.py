@@ -28,8 +28,8 @@ SEQ_FUSE = ((1, .5), (2, .5), (2, .5), (1, 1), (1, .5))
 # set "next", or None
 RINGS = (None, 0, None, 1, 2, None)
 
-# Every (N, L, params, field, tower, fp modes, sequence, extra) that
-# tests/test_gpu_time_step.py runs against the checker; tests/
+# Every (N, L, params, field, tower, fp modes, sequence, extra[, nsmooth, fuse,
+# shape]) that tests/test_gpu_time_step.py runs against the checker; tests/
 # test_time_step_fields.py holds the margins on the checker alone.  tower 0 / 1:
 # reference / correct; fp 0 / 1: bitwise / fma; extra: the separable source of
 # rings.source_factors plus the rings RINGS.
@@ -44,12 +44,38 @@ CASES = [
     (4096, 7, "easy", "generic", 0, (0, 1), SEQ_EASY, False),
     (4096, 7, "easy", "rank1", 0, (1,), SEQ_EASY, False),
     (4096, 7, "stiff", "generic", 0, (0, 1), SEQ_STIFF, False),
+    # other schedules (nsmooth, fuse, shape after the eight fields above; the
+    # defaults are 3, 3, 1): a W-cycle context whose coarsest level (n = 32) is
+    # solved inside the pair pass of the level above it, with the source and
+    # the rings, and a context whose smoothings are two passes of one sweep
+    # (generic0: on generic the (3, .75) step, 17 cycles, has a norm within
+    # 0.6 % of the tolerance)
+    (256, 4, "easy", "generic", 0, (0, 1), SEQ_EASY, True, 3, 3, 2),
+    (128, 3, "easy", "generic0", 0, (0, 1), SEQ_EASY, False, 2, 1, 1),
 ]
-CASE_PARAMS = [(N, L, p, f, tw, fp, seq, ex)
-               for N, L, p, f, tw, fps, seq, ex in CASES for fp in fps]
-CASE_IDS = ["N%d-L%d-%s-%s-t%d-%s%s" % (N, L, p, f, tw, "bitwise" if fp == 0 else "fma",
-                                        "-source-rings" if ex else "")
-            for N, L, p, f, tw, fp, seq, ex in CASE_PARAMS]
+SCHEDULE = (3, 3, 1)   # nsmooth, fuse, shape of a case that names none
+
+
+def _expand(cases):
+    out = []
+    for c in cases:
+        N, L, p, f, tw, fps, seq, ex = c[:8]
+        for fp in fps:
+            out.append((N, L, p, f, tw, fp, seq, ex) + (tuple(c[8:]) or SCHEDULE))
+    return out
+
+
+def _id(N, L, p, f, tw, fp, seq, ex, nsmooth, fuse, shape):
+    sched = "" if (nsmooth, fuse, shape) == SCHEDULE else "-s%df%d-%s" % (
+        nsmooth, fuse, "W" if shape == 2 else "V")
+    return "N%d-L%d-%s-%s-t%d-%s%s%s" % (N, L, p, f, tw, "bitwise" if fp == 0 else "fma",
+                                         "-source-rings" if ex else "", sched)
+
+
+# (N, L, params, field, tower, fp, sequence, extra, nsmooth, fuse, shape)
+CASE_PARAMS = _expand(CASES)
+CASE_IDS = [_id(*c) for c in CASE_PARAMS]
+CASE_ARGS = "N,L,pname,name,tower,fp,seq,extra,nsmooth,fuse,shape"
 
 
 def k_pair(dt, theta):
