@@ -50,12 +50,16 @@ def init_problem_rows(N: int, r0: int, r1: int, nthreads: int = 0):
 
 
 def timestepper(uT, u0, v1, v2, nu, maxlvl, n, dt, T, dx, tol, shape=1, *, nsmooth=3,
-                tower_mode=_lib.TOWER_REFERENCE, device=-1, fp_mode=_lib.FP_BITWISE):
-    """multigrid.cpp:124 -- run (int)(T/dt) CN steps; writes uT, returns cycles per step."""
+                tower_mode=_lib.TOWER_REFERENCE, device=-1, fp_mode=_lib.FP_BITWISE,
+                max_cycle=50, coarse_tol=1e-5, coarse_maxit=1000):
+    """multigrid.cpp:124 -- run (int)(T/dt) CN steps; writes uT, returns cycles per step.
+    A step that ends at max_cycle is not an error (multigrid.cpp:117-119 only
+    warns): its entry is max_cycle and the next step starts from its u."""
     steps = int(T / dt)
     cyc = (C.c_int * max(steps, 1))()
     opt = default_options(shape=shape, nsmooth=nsmooth, tower_mode=tower_mode, device=device,
-                          fp_mode=fp_mode)
+                          fp_mode=fp_mode, max_cycle=max_cycle, coarse_tol=coarse_tol,
+                          coarse_maxit=coarse_maxit)
     check(lib().mgx_timestepper_ex(_np_ptr(uT), _np_ptr(u0), _np_ptr(v1), _np_ptr(v2), nu,
                                    maxlvl, n, dt, T, dx, tol, C.byref(opt), cyc))
     return list(cyc)[:steps]
@@ -85,6 +89,10 @@ class Multigrid:
     ``local_parts=G`` for G virtual ranks on this GPU.  A partitioned solver
     takes the whole-solver calls (upload/download of the full grid, rhs,
     mg_inner, mg_outer, step, run_cycles, residual_norm(0)).
+
+    ``capped``: whether the last mg_outer / step / step_ex / step_bdf2 ran its
+    ``max_cycle`` cycles (MGX_E_NOCONV; also when the last allowed cycle itself
+    reached the tolerance), None before the first of them.
     """
 
     def __init__(self, N, maxlvl, dt, nu, *, nsmooth=3, shape=1,
@@ -93,6 +101,7 @@ class Multigrid:
                  world=1, rank=0, unique_id=None, local_parts=0, fp_mode=_lib.FP_BITWISE):
         self.N, self.maxlvl, self.dt, self.nu = N, maxlvl, dt, nu
         self.theta = 0.5   # Crank-Nicolson until set_time_step()
+        self.capped = None
         self.opt = default_options(nsmooth=nsmooth, shape=shape, tower_mode=tower_mode,
                                    device=device, smoother=smoother, fuse=fuse,
                                    coarse_tol=coarse_tol,
@@ -352,8 +361,9 @@ class Multigrid:
         theta-step (step()) starts it.  Zero-stability needs dt / dt_prev < 1 +
         sqrt(2); nothing is refused."""
         cyc, r0, r = C.c_int(), C.c_double(), C.c_double()
-        check(lib().mgx_step_bdf2(self._h, tol, C.byref(cyc), C.byref(r0), C.byref(r)),
-              allow=(_lib.MGX_E_NOCONV,))
+        rc = check(lib().mgx_step_bdf2(self._h, tol, C.byref(cyc), C.byref(r0), C.byref(r)),
+                   allow=(_lib.MGX_E_NOCONV,))
+        self.capped = rc == _lib.MGX_E_NOCONV
         return cyc.value, r0.value, r.value
 
     def rollback(self):
@@ -521,19 +531,23 @@ class Multigrid:
         cyc, r0, r = C.c_int(), C.c_double(), C.c_double()
         rc = check(lib().mgx_mg_outer(self._h, tol, C.byref(cyc), C.byref(r0), C.byref(r)),
                    allow=(_lib.MGX_E_NOCONV,))
-        return cyc.value, r0.value, r.value, rc == _lib.MGX_E_NOCONV
+        self.capped = rc == _lib.MGX_E_NOCONV
+        return cyc.value, r0.value, r.value, self.capped
 
     def step(self, tol=1e-6):
+        """One time step -> cycles; a cap hit is reported in self.capped."""
         cyc = C.c_int()
-        check(lib().mgx_step(self._h, tol, C.byref(cyc)), allow=(_lib.MGX_E_NOCONV,))
+        rc = check(lib().mgx_step(self._h, tol, C.byref(cyc)), allow=(_lib.MGX_E_NOCONV,))
+        self.capped = rc == _lib.MGX_E_NOCONV
         return cyc.value
 
     def step_ex(self, tol=1e-6):
         """step() -> (cycles, res0, res): with mg_outer's initial and last
         residual norm (mgx_step_ex)."""
         cyc, r0, r = C.c_int(), C.c_double(), C.c_double()
-        check(lib().mgx_step_ex(self._h, tol, C.byref(cyc), C.byref(r0), C.byref(r)),
-              allow=(_lib.MGX_E_NOCONV,))
+        rc = check(lib().mgx_step_ex(self._h, tol, C.byref(cyc), C.byref(r0), C.byref(r)),
+                   allow=(_lib.MGX_E_NOCONV,))
+        self.capped = rc == _lib.MGX_E_NOCONV
         return cyc.value, r0.value, r.value
 
     def run_cycles(self, cycles):

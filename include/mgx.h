@@ -32,7 +32,8 @@ extern "C" {
 #define MGX_E_ARG 1     /* invalid argument (sizes, level, null pointer) */
 #define MGX_E_HIP 2     /* a HIP runtime call failed */
 #define MGX_E_RCCL 3    /* an RCCL call failed */
-#define MGX_E_NOCONV 4  /* mg_outer hit its cycle cap (reported, not fatal) */
+#define MGX_E_NOCONV 4  /* mg_outer ran max_cycle cycles (reported, not fatal; also
+                           when the last of them reached the tolerance) */
 #define MGX_E_INTERNAL 5 /* an internal consistency check failed (a bug) */
 
 const char *mgx_last_error(void);
@@ -100,6 +101,15 @@ typedef struct mgx_options {
  * compute_rhs are always bitwise).
  * MGX_FP_BITWISE: the reference's expressions term by term, no contraction,
  *   the correctly rounded division -- u bitwise equal to the serial reference.
+ *   Domain: finite fields whose update numerators a = rhs - sum(coef * u) are
+ *   zero or at least 2^-969 (2e-292) in magnitude.  The fused passes divide
+ *   by the diagonal with a reciprocal and one correction step, whose
+ *   remainder must not underflow (tools/check_division.c).  Below 2^-969 a
+ *   quotient is within one ulp of the reference's (first seen near 2^-1003,
+ *   1e-302); the coarsest solve and smoothers 1 / 2 use the true division, so
+ *   down there two kernels of this library may differ from each other by that
+ *   ulp on the same point.  A numerator of +-Inf gives NaN where the reference
+ *   gives +-Inf; NaN and +-0 give what the reference gives.
  * MGX_FP_FMA: the operator divided by its diagonal and contracted: each
  *   update u = f/d + m_N uN + m_W uW + m_E uE + m_S uS as four fused
  *   multiply-adds (m = -coefficient/d), residuals d*(update - u) -- within a
@@ -157,7 +167,12 @@ int mgx_prolong_add(mgx_ctx *ctx, int level);
 /* One V- (or W-) cycle from the finest level: mg_inner(lvl=0) (multigrid.cpp:17-92). */
 int mgx_vcycle(mgx_ctx *ctx);
 /* mg_outer (multigrid.cpp:97-120): cycles until ||r||/||r0|| <= tol or the cap.
- * Any output pointer may be NULL.  Returns MGX_E_NOCONV when the cap is hit. */
+ * Any output pointer may be NULL.  Returns MGX_E_NOCONV when the cap is hit:
+ * whenever *cycles == max_cycle, also when that last allowed cycle reached the
+ * tolerance (compare *res / *res0 with tol to tell).  u, *cycles and the norms
+ * are then those of the max_cycle cycles, and the context is ready for the next
+ * call.  A non-finite initial norm runs no cycle and returns MGX_OK, as the
+ * reference's loop does.  mgx_timestepper[_ex] steps on after a capped step. */
 int mgx_mg_outer(mgx_ctx *ctx, double tol, int *cycles, double *res0, double *res);
 /* One timestep: mgx_rhs + mgx_mg_outer (multigrid.cpp:165-172). */
 int mgx_step(mgx_ctx *ctx, double tol, int *cycles);

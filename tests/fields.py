@@ -43,6 +43,9 @@ PARAMS = {
     "visc16": (lambda N: 1.0 / N, lambda N: -1.6 / N),
     "visc07": (lambda N: 1.0 / N, lambda N: -0.7 / N),
     "visc06": (lambda N: 1.0 / N, lambda N: -0.6 / N),
+    # the diverging set named above, for the tests of the cycle cap
+    # (tests/exits.py): at N=4096 the norm falls for two cycles, then grows
+    "grow3": (lambda N: 3.0 / N, -2e-3),
 }
 
 
