@@ -7,6 +7,7 @@ missing or fails to load, every entry point raises.
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -54,6 +55,41 @@ class Stats(C.Structure):
 
     def __repr__(self):
         return "Stats(" + ", ".join(f"{f}={getattr(self, f)!r}" for f, _ in self._fields_) + ")"
+
+
+class StepErr(C.Structure):
+    """mgx_step_err (include/mgx.h): 11 eight-byte fields."""
+    _fields_ = [("count", C.c_long), ("nonfinite", C.c_long), ("w", C.c_double),
+                ("err_sum_sq", C.c_double), ("err_max", C.c_double), ("err_max_i", C.c_long),
+                ("err_max_j", C.c_long), ("d_sum_sq", C.c_double), ("d_max", C.c_double),
+                ("c_sum_sq", C.c_double), ("c_max", C.c_double)]
+
+
+class StepError:
+    """The record of mgx_step_error as Python values: the fields of
+    mgx_step_err, plus rms = sqrt(err_sum_sq / (count - nonfinite)), the
+    weighted RMS norm of e a controller compares with 1 (NaN when no point is
+    finite)."""
+    FIELDS = tuple(f for f, _ in StepErr._fields_)
+
+    def __init__(self, rec: StepErr):
+        for f in self.FIELDS:
+            setattr(self, f, getattr(rec, f))
+
+    @property
+    def rms(self):
+        m = self.count - self.nonfinite
+        return math.sqrt(self.err_sum_sq / m) if m > 0 else math.nan
+
+    def astuple(self):
+        return tuple(getattr(self, f) for f in self.FIELDS)
+
+    def record(self) -> StepErr:
+        return StepErr(*self.astuple())
+
+    def __repr__(self):
+        return "StepError(" + ", ".join(f"{f}={getattr(self, f)!r}" for f in self.FIELDS) + \
+            f", rms={self.rms!r})"
 
 
 _dp = C.POINTER(C.c_double)
@@ -154,6 +190,12 @@ _SIGS = {
     "mgx_step_bdf2": (_I, [_vp, _D, C.POINTER(_I), _dp, _dp]),
     "mgx_rollback": (_I, [_vp]),
     "mgx_compute_rhs_bdf2": (_I, [_vp, _vp, _vp, _L, _D, _D, _vp, _D]),
+    "mgx_set_history_depth": (_I, [_vp, _I]),
+    "mgx_history_depth": (_I, [_vp, C.POINTER(_I), C.POINTER(_I), _dp]),
+    "mgx_step_error": (_I, [_vp, _D, _D, C.POINTER(StepErr)]),
+    "mgx_step_error_rows": (_I, [_vp, _I, _D, _D, C.POINTER(StepErr)]),
+    "mgx_step_err_merge": (_I, [C.POINTER(StepErr), C.POINTER(StepErr)]),
+    "mgx_array_step_error": (_I, [_vp, _vp, _vp, _L, _D, _D, _D, C.POINTER(StepErr)]),
     "mgx_build_id": (C.c_char_p, []),
     "mgx_build_sources_id": (C.c_char_p, []),
 }
@@ -309,6 +351,41 @@ def stats_merge(a: Stats, b: Stats) -> Stats:
     other = Stats.from_buffer_copy(b)
     check(lib().mgx_stats_merge(C.byref(out), C.byref(other)))
     return out
+
+
+def array_step_error(u, h, h2, n, w, atol, rtol) -> StepError:
+    """mgx_array_step_error: the step error record of three device arrays in
+    the reference layout ((n+1)^2 float64, any n >= 2) -- u^(n+1), u^n, u^(n-1)
+    -- with w = dt_prev / dt_prev2.  Null stream; synchronises."""
+    cnt = (n + 1) * (n + 1)
+    s = StepErr()
+    check(lib().mgx_array_step_error(device_ptr(u, cnt, "u"), device_ptr(h, cnt, "h"),
+                                     device_ptr(h2, cnt, "h2"), n, float(w), float(atol),
+                                     float(rtol), C.byref(s)))
+    return StepError(s)
+
+
+def step_err_merge(a, b) -> StepError:
+    """mgx_step_err_merge: the record of the union of two disjoint sets of
+    points of one step (host only); neither argument is changed.  Raises
+    MGXError (MGX_E_ARG) when the records' w differ."""
+    out = a.record() if isinstance(a, StepError) else StepErr.from_buffer_copy(a)
+    other = b.record() if isinstance(b, StepError) else StepErr.from_buffer_copy(b)
+    check(lib().mgx_step_err_merge(C.byref(out), C.byref(other)))
+    return StepError(out)
+
+
+def next_dt(dt, err, order, safety=0.9, fmin=0.2, fmax=2.0):
+    """The usual step-size rule (host only): dt * clip(safety * err**(-1/order),
+    fmin, fmax) for an error measure err (StepError.rms, say) that a step
+    passes at err <= 1.  err == 0 gives dt * fmax, a NaN or infinite err dt *
+    fmin."""
+    err = float(err)
+    if not math.isfinite(err):
+        return dt * fmin
+    if err == 0.0:
+        return dt * fmax
+    return dt * min(fmax, max(fmin, safety * abs(err) ** (-1.0 / order)))
 
 
 def factor_velocity_device(v, n, ld=None, smin=0.0):

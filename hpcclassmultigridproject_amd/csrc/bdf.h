@@ -33,8 +33,10 @@ Coefs coefficients(double dt, double dt_prev);
 // a.partials / a.norm_out are required; interior rows of [a.ra, a.rb) and
 // a.take_sqrt as there.  h: the history, the layout of a.u (h + r*pitch =
 // global row r); every row of [a.ra, a.rb) of it is overwritten with u's.
-void launch_rhs_norm_bdf(const mgxsrc::SrcArgs &a, double *h, double b0, double b1,
-                         hipStream_t s);
+// hin: where u^(n-1) is read -- h itself (a history of depth 1), or the other
+// array of a history of depth 2, the same layout.
+void launch_rhs_norm_bdf(const mgxsrc::SrcArgs &a, const double *hin, double *h, double b0,
+                         double b1, hipStream_t s);
 
 // reference layout (pitch n+1, one point per lane), the gs.h-style raw op: the
 // interior of rhs alone is written; f may be null

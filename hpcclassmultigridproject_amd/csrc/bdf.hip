@@ -44,9 +44,12 @@ namespace {
 // the grid's row 0) from the `un` of the first group and row r_end (edges & 2:
 // the grid's row n) from the last row the last group loaded.  Whole pairs are stored, so the ring's columns and the zero padding
 // behind column n travel with their rows.  u is only read.
+// hin is where u^(n-1) is read and h where u^n is stored: the same address with
+// a history of depth 1, the two arrays of depth 2 (mgx_set_history_depth) --
+// so neither is __restrict__.  Only the lane that stores a pair has read it.
 template <int SRC, bool SV>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void k_rhs_norm_bdf(
-    const double *__restrict__ u, double *__restrict__ h, const double *__restrict__ v1,
+    const double *__restrict__ u, const double *hin, double *h, const double *__restrict__ v1,
     const double *__restrict__ v2, const double *__restrict__ sa1, const double *__restrict__ sb1,
     const double *__restrict__ sa2, const double *__restrict__ sb2,
     const double *__restrict__ f, const double *__restrict__ fa, const double *__restrict__ fb,
@@ -93,7 +96,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void k
         double2 x2 = z2, y2 = z2, s2 = z2, hm = z2;
         if (act) {
             us = ld2(u + o + pitch + c0);
-            hm = ld2(h + o + c0);   // u^(n-1): read once, then replaced
+            hm = ld2(hin + o + c0);   // u^(n-1): read once, then replaced (hin == h)
             if (SRC == 2) {
                 const long fw = n + 1;
                 const double a0 = fa[i];
@@ -160,21 +163,21 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void k
 }
 
 template <int SRC, bool SV>
-void launch_inst(const mgxsrc::SrcArgs &a, double *h, double b0, double b1, dim3 g, int R, int f,
-                 int e, int edges, hipStream_t s) {
-    MGX_LAUNCH((k_rhs_norm_bdf<SRC, SV>), g, dim3(256), s, a.u, h, a.v1, a.v2, a.sa1, a.sb1, a.sa2,
-               a.sb2, a.f, a.fa, a.fb, a.terms, a.cf, b0, b1, (int)a.n, a.pitch, a.c, R, a.rhs,
-               a.partials, f, e, edges);
+void launch_inst(const mgxsrc::SrcArgs &a, const double *hin, double *h, double b0, double b1,
+                 dim3 g, int R, int f, int e, int edges, hipStream_t s) {
+    MGX_LAUNCH((k_rhs_norm_bdf<SRC, SV>), g, dim3(256), s, a.u, hin, h, a.v1, a.v2, a.sa1, a.sb1,
+               a.sa2, a.sb2, a.f, a.fa, a.fb, a.terms, a.cf, b0, b1, (int)a.n, a.pitch, a.c, R,
+               a.rhs, a.partials, f, e, edges);
 }
 template <bool SV>
-void launch_form(const mgxsrc::SrcArgs &a, double *h, double b0, double b1, dim3 g, int R, int f,
-                 int e, int edges, hipStream_t s) {
+void launch_form(const mgxsrc::SrcArgs &a, const double *hin, double *h, double b0, double b1,
+                 dim3 g, int R, int f, int e, int edges, hipStream_t s) {
     if (a.terms > 0)
-        launch_inst<2, SV>(a, h, b0, b1, g, R, f, e, edges, s);
+        launch_inst<2, SV>(a, hin, h, b0, b1, g, R, f, e, edges, s);
     else if (a.f)
-        launch_inst<1, SV>(a, h, b0, b1, g, R, f, e, edges, s);
+        launch_inst<1, SV>(a, hin, h, b0, b1, g, R, f, e, edges, s);
     else
-        launch_inst<0, SV>(a, h, b0, b1, g, R, f, e, edges, s);
+        launch_inst<0, SV>(a, hin, h, b0, b1, g, R, f, e, edges, s);
 }
 
 // the frame of k_raw_rhs_source
@@ -199,9 +202,10 @@ __global__ __launch_bounds__(256) void k_raw_rhs_bdf(double *rhs, const double *
 
 }  // namespace
 
-void launch_rhs_norm_bdf(const mgxsrc::SrcArgs &a, double *h, double b0, double b1,
-                         hipStream_t s) {
-    if (!a.partials || !a.norm_out || !h || a.terms < 0 || a.terms > mgxsrc::kMaxTerms) return;
+void launch_rhs_norm_bdf(const mgxsrc::SrcArgs &a, const double *hin, double *h, double b0,
+                         double b1, hipStream_t s) {
+    if (!a.partials || !a.norm_out || !h || !hin || a.terms < 0 || a.terms > mgxsrc::kMaxTerms)
+        return;
     int ra = a.ra, rb = a.rb;
     if (rb < 0) {
         ra = 0;
@@ -215,9 +219,9 @@ void launch_rhs_norm_bdf(const mgxsrc::SrcArgs &a, double *h, double b0, double 
     int R;
     mgxsrc::res_grid(a.n, e - f, g, R);   // launch_residual_norm's cut of the rows
     if (a.sa1 && a.sb1 && a.sa2 && a.sb2)
-        launch_form<true>(a, h, b0, b1, g, R, f, e, edges, s);
+        launch_form<true>(a, hin, h, b0, b1, g, R, f, e, edges, s);
     else
-        launch_form<false>(a, h, b0, b1, g, R, f, e, edges, s);
+        launch_form<false>(a, hin, h, b0, b1, g, R, f, e, edges, s);
     launch_norm_final(a.partials, (int)(g.x * g.y), a.norm_out, a.take_sqrt ? 1 : 0, s);
 }
 

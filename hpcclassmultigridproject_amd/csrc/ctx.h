@@ -113,6 +113,16 @@ struct mgx_ctx {
     double *hist = nullptr;
     bool hist_on = false, hist_valid = false;
     double hist_dt = 0;
+    // mgx_set_history_depth(ctx, 2): hist2 = a second array in the layout of
+    // hist (in every part / sub-context as hist is; hist2_on here), u^(n-1)
+    // after a step.  Every step stores its snapshot into the older buffer and
+    // exchanges the two pointers; hist2_valid / hist2_dt are what hist_valid /
+    // hist_dt were before the step.  hist_rolled: mgx_rollback has just moved
+    // u^(n-1) into hist, so hist is no longer the u to go back to.
+    double *hist2 = nullptr;
+    bool hist2_on = false, hist2_valid = false, hist_rolled = false;
+    double hist2_dt = 0;
+    void hist_invalidate() { hist_valid = hist2_valid = hist_rolled = false; }
     mgx_options opt{};
     std::vector<mgxi::Level> lv;
     double *partials = nullptr;   // norm partial sums
@@ -293,6 +303,28 @@ int hist_restore_ctx(mgx_ctx *c);
 // every sub-context where all levels are replicated.  dist_rhs_norm_bdf mirrors
 // dist_rhs_norm's two-operator branch: the u ghosts before, the rhs ghosts after
 int dist_set_history(mgx_ctx *c, int on, const char *who);
+// mgx_set_history_depth (1 <-> 2) on one context's own state: hist2 allocated
+// and zeroed (hist too while it holds nothing valid: a pass stores whole column
+// pairs up to column n, the pad columns behind them must stay zeros), or freed
+int hist2_alloc_ctx(mgx_ctx *c, bool zero_hist, const char *who);
+void hist2_free_ctx(mgx_ctx *c);
+// ... and on every part or sub-context (all or none); zero_hist as above
+int dist_set_history2(mgx_ctx *c, int on, bool zero_hist, const char *who);
+// depth 2, before a step's snapshot or BDF2 pass: hist <-> hist2 in the context
+// (every part / sub-context), so that the pass writes the older buffer
+void hist_swap(mgx_ctx *c);
+void dist_hist_swap(mgx_ctx *c);
+// mgx_step_error[_rows] (csrc/errest.h; mgx.hip): the record of interior rows
+// of [r0, r1) of three arrays in one tower layout, on c's stream and
+// diagnostics scratch.  Synchronises the stream.
+int step_error_view(mgx_ctx *c, const double *u, const double *h, const double *h2, long row0,
+                    long pitch, long n, long r0, long r1, double w, double atol, double rtol,
+                    mgx_step_err *out);
+// ... on a partitioned context (dist.hip): the owned rows of one local part,
+// and the merge of the parts' records in part order (local parts only)
+int dist_step_error_rows(mgx_ctx *c, int part, double w, double atol, double rtol,
+                         mgx_step_err *out, const char *who);
+int dist_step_error(mgx_ctx *c, double w, double atol, double rtol, mgx_step_err *out);
 int dist_snapshot(mgx_ctx *c);
 int dist_rhs_norm_bdf(mgx_ctx *c, double b0, double b1, double cf, double *res0);
 int dist_rollback(mgx_ctx *c);
@@ -331,9 +363,12 @@ struct SamplePiece {
 // the kernel (device out).  Synchronises the stream.
 int sample_pieces(mgx_ctx *c, const std::vector<SamplePiece> &pieces, long stride, long A0,
                   long rows, double *out, bool device_out);
-// the field mgx_download_level(level, field) copies (4 = the source copy) of a
-// single-GPU context
+// the field mgx_download_level(level, field) copies (4 = the source copy, 5 / 6
+// = the history arrays hist / hist2) of a single-GPU context
 int field_view(mgx_ctx *c, int level, int field, mgxdiag::View *v);
+// fields 5 / 6 = the history arrays hist / hist2 (level 0): MGX_E_ARG where the
+// array is absent or not valid by c's flags; host only
+int history_field_check(const mgx_ctx *c, int level, int field, const char *who);
 
 // dist.hip entry points used by the C ABI
 int dist_upload(mgx_ctx *c, const double *u0, const double *v1, const double *v2,

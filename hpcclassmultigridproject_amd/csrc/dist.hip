@@ -38,6 +38,7 @@
 #include "source.h"
 #include "tstep.h"
 #include "bdf.h"
+#include "errest.h"
 
 namespace mgxi {
 
@@ -123,6 +124,8 @@ struct PLevel {
     // level 0: the history of mgx_set_history (mgx_ctx::hist), the layout of a u
     // buffer -- its owned rows [ra, rb) are the part's share of u^n -- or null
     double *hist = nullptr;
+    // level 0: the second array of a history of depth 2 (mgx_ctx::hist2), or null
+    double *hist2 = nullptr;
     // level 0: exact velocity factors (sepvel.h) indexed by GLOBAL row / column
     // (full-length arrays, this block's rows filled), or null
     double *sa1 = nullptr, *sb1 = nullptr, *sa2 = nullptr, *sb2 = nullptr;
@@ -209,6 +212,7 @@ void dist_free(mgx_ctx *c) {
             (void)hipFree(L.src_a);
             (void)hipFree(L.src_b);
             (void)hipFree(L.hist);
+            (void)hipFree(L.hist2);
             for (double *f : {L.sa1, L.sb1, L.sa2, L.sb2}) (void)hipFree(f);
         }
         if (p.sub) free_ctx(p.sub);
@@ -1304,6 +1308,8 @@ int dist_set_history(mgx_ctx *c, int on, const char *who) {
             } else {
                 (void)hipFree(p.lv[0].hist);
                 p.lv[0].hist = nullptr;
+                (void)hipFree(p.lv[0].hist2);
+                p.lv[0].hist2 = nullptr;
             }
         }
     };
@@ -1330,6 +1336,58 @@ int dist_set_history(mgx_ctx *c, int on, const char *who) {
     }
     if (rc != MGX_OK) free_all();   // all parts or none
     return rc;
+}
+// mgx_set_history_depth (1 <-> 2): the second array of every part or
+// sub-context, zeroed (all parts or none); zero_hist: the first one too
+int dist_set_history2(mgx_ctx *c, int on, bool zero_hist, const char *who) {
+    Dist *d = c->dist;
+    HIPCHK(hipSetDevice(c->device));
+    CHK(settle(c));
+    auto free_all = [&] {
+        (void)hipStreamSynchronize(c->stream);   // a pass may still read it
+        for (auto &p : d->parts) {
+            if (d->la == 0) {
+                hist2_free_ctx(p.sub);
+            } else {
+                (void)hipFree(p.lv[0].hist2);
+                p.lv[0].hist2 = nullptr;
+            }
+        }
+    };
+    if (!on) {
+        free_all();
+        return MGX_OK;
+    }
+    int rc = MGX_OK;
+    for (auto &p : d->parts) {
+        if (rc != MGX_OK) break;
+        if (d->la == 0) {
+            rc = hist2_alloc_ctx(p.sub, zero_hist, who);
+            continue;
+        }
+        PLevel &L = p.lv[0];
+        hipError_t e = hipSuccess;
+        if (!L.hist2 && (e = hipMalloc(&L.hist2, L.bytes())) != hipSuccess) L.hist2 = nullptr;
+        if (e == hipSuccess) e = hipMemsetAsync(L.hist2, 0, L.bytes(), c->stream);
+        if (e == hipSuccess && zero_hist) e = hipMemsetAsync(L.hist, 0, L.bytes(), c->stream);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            rc = fail(MGX_E_HIP, std::string(who) + ": no room for the part's second history "
+                                                    "array (one finest-level block): " +
+                                     hipGetErrorString(e));
+        }
+    }
+    if (rc != MGX_OK) free_all();   // all parts or none
+    return rc;
+}
+void dist_hist_swap(mgx_ctx *c) {
+    Dist *d = c->dist;
+    for (auto &p : d->parts) {
+        if (d->la == 0)
+            std::swap(p.sub->hist, p.sub->hist2);
+        else
+            std::swap(p.lv[0].hist, p.lv[0].hist2);
+    }
 }
 // h = what mgx_download would return: every part's owned rows (whole pitched
 // rows, contiguous), or every sub-context's u
@@ -1372,8 +1430,10 @@ int dist_rhs_norm_bdf(mgx_ctx *c, double b0, double b1, double cf, double *res0)
         A.cf = cf;
         const bool field = A.f && !A.terms;
         cb = ((A.sa1 ? 32.0 : 48.0) + (field ? 8.0 : 0.0)) * L.Mown();
+        // (depth 2: mgx.hip has exchanged the arrays; u^(n-1) lies in hist2)
+        const double *hin = L.F(L.hist2 ? L.hist2 : L.hist);
         CHK(launch(c, MGX_K_RHS, 0, (field ? 96.0 : 88.0) * L.Mown(), cb, [&] {
-            mgxbdf::launch_rhs_norm_bdf(A, L.F(L.hist), b0, b1, c->stream);
+            mgxbdf::launch_rhs_norm_bdf(A, hin, L.F(L.hist), b0, b1, c->stream);
         }));
     }
     CHK(xchg(c, 0, kRhs));
@@ -1730,13 +1790,19 @@ int dist_download_rows(mgx_ctx *c, int part, double *out, hipMemcpyKind kind) {
 // replicated it is the part's full copy in its sub-context.  Host checks
 // first; the only device call is the sub-context's materialize.
 static const char *const kSepNoCopy = ": the source is separable: no copy of it is kept (field 4)";
+// fields 5 / 6: a part's history arrays, valid by the flags c keeps for all parts
+static int field_range(mgx_ctx *c, int field, const std::string &who) {
+    if (field < 0 || field > 6)
+        return fail(MGX_E_ARG, who + ": field must be 0..6 (u, rhs, v1, v2, source, history, "
+                                     "history2)");
+    return history_field_check(c, 0, field, who.c_str());
+}
 static int part_view(mgx_ctx *c, int part, int field, const char *who, mgxdiag::View *v, int *ra,
                      int *rb) {
     Dist *d = c->dist;
     if (part < 0 || part >= (int)d->parts.size())
         return fail(MGX_E_ARG, std::string(who) + ": bad part");
-    if (field < 0 || field > 4)
-        return fail(MGX_E_ARG, std::string(who) + ": field must be 0..4 (u, rhs, v1, v2, source)");
+    CHK(field_range(c, field, who));
     plan_rows(c->N, 0, d->world, d->parts[part].rank, ra, rb);
     if (d->la == 0) {
         mgx_ctx *s = d->parts[part].sub;
@@ -1748,7 +1814,7 @@ static int part_view(mgx_ctx *c, int part, int field, const char *who, mgxdiag::
     if (field == 4 && L.src_terms) return fail(MGX_E_ARG, std::string(who) + kSepNoCopy);
     if (field == 4 && !L.src) return fail(MGX_E_ARG, std::string(who) + ": no source is set");
     v->a = field == 0 ? L.u[L.cur] : field == 1 ? L.rhs : field == 2 ? L.v1 : field == 3 ? L.v2
-                                                                                         : L.src;
+         : field == 4 ? L.src : field == 5 ? L.hist : L.hist2;
     v->row0 = field == 4 ? L.ra : L.lo;   // the source copy holds the owned rows only
     v->pitch = L.pitch;
     v->n = L.n;
@@ -1776,8 +1842,7 @@ int dist_field_stats(mgx_ctx *c, int level, int field, int interior, const doubl
     if (level != 0)
         return fail(MGX_E_ARG, "mgx_field_stats: only level 0 is available on a partitioned "
                                "context");
-    if (field < 0 || field > 4)
-        return fail(MGX_E_ARG, "mgx_field_stats: field must be 0..4 (u, rhs, v1, v2, source)");
+    CHK(field_range(c, field, who));
     if (field == 4 && c->src_active && c->src_terms)
         return fail(MGX_E_ARG, std::string(who) + kSepNoCopy);
     if (field == 4 && !c->src_active) return fail(MGX_E_ARG, "mgx_field_stats: no source is set");
@@ -1805,6 +1870,54 @@ int dist_field_stats(mgx_ctx *c, int level, int field, int interior, const doubl
     return MGX_OK;
 }
 
+// mgx_step_error_rows: the owned rows of local part `part` -- u by part_view's
+// route, the part's two history arrays beside it (one layout: rows from lo, or
+// the sub-context's full copies where every level is replicated).  `from`: the
+// part whose arrays are read (the whole-grid call reads sub-context 0's).
+static int step_error_part(mgx_ctx *c, int part, int from, double w, double atol, double rtol,
+                           mgx_step_err *out, const char *who) {
+    Dist *d = c->dist;
+    if (part < 0 || part >= (int)d->parts.size())
+        return fail(MGX_E_ARG, std::string(who) + ": bad part");
+    HIPCHK(hipSetDevice(c->device));
+    CHK(settle(c));
+    mgxdiag::View v;
+    int ra, rb, r0, r1;
+    CHK(part_view(c, from, 0, who, &v, &r0, &r1));
+    plan_rows(c->N, 0, d->world, d->parts[part].rank, &ra, &rb);
+    const double *h, *h2;
+    if (d->la == 0) {
+        h = d->parts[from].sub->hist;
+        h2 = d->parts[from].sub->hist2;
+    } else {
+        h = d->parts[from].lv[0].hist;
+        h2 = d->parts[from].lv[0].hist2;
+    }
+    return step_error_view(c, v.a, h, h2, v.row0, v.pitch, v.n, ra, rb, w, atol, rtol, out);
+}
+int dist_step_error_rows(mgx_ctx *c, int part, double w, double atol, double rtol,
+                         mgx_step_err *out, const char *who) {
+    return step_error_part(c, part, part, w, atol, rtol, out, who);
+}
+int dist_step_error(mgx_ctx *c, double w, double atol, double rtol, mgx_step_err *out) {
+    Dist *d = c->dist;
+    if (!d->local)
+        return fail(MGX_E_ARG, "mgx_step_error: an RCCL rank holds its own rows and this call "
+                               "does not communicate: call mgx_step_error_rows on every rank "
+                               "and combine the records with mgx_step_err_merge");
+    for (int p = 0; p < (int)d->parts.size(); ++p) {
+        mgx_step_err s;
+        // every level replicated: sub-context 0 holds the grid; the same row
+        // cut, so that the record is the merge of the parts' either way
+        CHK(step_error_part(c, p, d->la == 0 ? 0 : p, w, atol, rtol, &s, "mgx_step_error"));
+        if (p == 0)
+            *out = s;
+        else
+            mgxerr::merge(out, s);
+    }
+    return MGX_OK;
+}
+
 static int check_stride(long n, long stride, const char *who) {
     if (stride < 1 || stride > n || n % stride)
         return fail(MGX_E_ARG, std::string(who) + ": stride must divide the level's n (1 <= "
@@ -1826,8 +1939,7 @@ int dist_sample(mgx_ctx *c, int level, int field, long stride, double *out, bool
     if (level != 0)
         return fail(MGX_E_ARG, std::string(who) + ": only level 0 is available on a partitioned "
                                                   "context");
-    if (field < 0 || field > 4)
-        return fail(MGX_E_ARG, std::string(who) + ": field must be 0..4 (u, rhs, v1, v2, source)");
+    CHK(field_range(c, field, who));
     if (field == 4 && c->src_active && c->src_terms)
         return fail(MGX_E_ARG, std::string(who) + kSepNoCopy);
     if (field == 4 && !c->src_active) return fail(MGX_E_ARG, std::string(who) + ": no source is set");
@@ -1856,8 +1968,7 @@ int dist_sample_rows(mgx_ctx *c, int part, int field, long stride, double *out, 
     Dist *d = c->dist;
     if (part < 0 || part >= (int)d->parts.size())
         return fail(MGX_E_ARG, "mgx_sample_rows: bad part");
-    if (field < 0 || field > 4)
-        return fail(MGX_E_ARG, "mgx_sample_rows: field must be 0..4 (u, rhs, v1, v2, source)");
+    CHK(field_range(c, field, who));
     if (field == 4 && c->src_active && c->src_terms)
         return fail(MGX_E_ARG, std::string(who) + kSepNoCopy);
     if (field == 4 && !c->src_active) return fail(MGX_E_ARG, "mgx_sample_rows: no source is set");
@@ -2232,7 +2343,7 @@ int mgx_upload_rows(mgx_ctx *c, const double *const *u0, const double *const *v1
                     const double *const *v2) {
     if (!c || !c->dist) return fail(MGX_E_ARG, "mgx_upload_rows: not a partitioned context");
     c->bc_pending = false;   // a pending ring belongs to the old u (mgx_upload)
-    c->hist_valid = false;   // ... and so does a history
+    c->hist_invalidate();   // ... and so does a history
     return dist_upload_rows_impl(c, u0, v1, v2);
 }
 

@@ -23,6 +23,7 @@
 #include "source.h"
 #include "tstep.h"
 #include "bdf.h"
+#include "errest.h"
 #include "vfactor.h"
 
 namespace mgxi {
@@ -977,8 +978,11 @@ int op_rhs_norm_bdf(mgx_ctx *c, double b0, double b1, double cf, double *res0) {
     const bool field = A.f && !A.terms;
     // u and h in, h and rhs out (+ f of a field source) (+ v1, v2 without factors)
     cb = ((A.sa1 ? 32.0 : 48.0) + (field ? 8.0 : 0.0)) * L.M();
+    // depth 2: the caller has exchanged the two arrays (hist_swap), u^(n-1) is
+    // read from hist2 and u^n stored into hist -- the same bytes
+    const double *hin = c->hist2 ? c->hist2 : c->hist;
     CHK(launch(c, MGX_K_RHS, 0, (field ? 96.0 : 88.0) * L.M(), cb,
-               [&] { mgxbdf::launch_rhs_norm_bdf(A, c->hist, b0, b1, c->stream); }));
+               [&] { mgxbdf::launch_rhs_norm_bdf(A, hin, c->hist, b0, b1, c->stream); }));
     return read_norm(c, res0);
 }
 
@@ -1001,6 +1005,38 @@ void hist_free_ctx(mgx_ctx *c) {
     (void)hipStreamSynchronize(c->stream);   // a pass may still read it
     (void)hipFree(c->hist);
     c->hist = nullptr;
+    (void)hipFree(c->hist2);
+    c->hist2 = nullptr;
+}
+int hist2_alloc_ctx(mgx_ctx *c, bool zero_hist, const char *who) {
+    const Level &L = c->lv[0];
+    const size_t bytes = sizeof(double) * (size_t)(L.n + 1) * (size_t)L.pitch;
+    if (!c->hist2) {
+        hipError_t e = hipMalloc(&c->hist2, bytes);
+        if (e == hipSuccess && (e = hipMemsetAsync(c->hist2, 0, bytes, c->stream)) != hipSuccess)
+            (void)hipFree(c->hist2);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            c->hist2 = nullptr;
+            return fail(MGX_E_HIP, std::string(who) + ": no room for the second history array "
+                                                      "(one finest-level array): " +
+                                       hipGetErrorString(e));
+        }
+    }
+    if (zero_hist) HIPCHK(hipMemsetAsync(c->hist, 0, bytes, c->stream));
+    return MGX_OK;
+}
+void hist2_free_ctx(mgx_ctx *c) {
+    if (!c->hist2) return;
+    (void)hipStreamSynchronize(c->stream);   // a pass may still read it
+    (void)hipFree(c->hist2);
+    c->hist2 = nullptr;
+}
+void hist_swap(mgx_ctx *c) {
+    if (c->dist)
+        dist_hist_swap(c);
+    else
+        std::swap(c->hist, c->hist2);
 }
 int hist_snapshot_ctx(mgx_ctx *c) {
     CHK(materialize(c, 0));
@@ -1327,6 +1363,7 @@ void free_ctx(mgx_ctx *c) {
     (void)hipFree(c->diag);
     (void)hipFree(c->bc_buf);
     (void)hipFree(c->hist);
+    (void)hipFree(c->hist2);
     c->bc_timer.destroy();
     if (c->hscal) (void)hipHostFree(c->hscal);
     for (auto &r : c->pending) {
@@ -1829,13 +1866,13 @@ int mgx_compute_rhs_source(double *rhs, const double *u, long n, const double *v
 // every upload cancels it)
 int mgx_upload(mgx_ctx *c, const double *u0, const double *v1, const double *v2) {
     if (c) c->bc_pending = false;
-    if (c) c->hist_valid = false;   // (a history belongs to the old u too)
+    if (c) c->hist_invalidate();   // (a history belongs to the old u too)
     if (c && c->dist) return dist_upload(c, u0, v1, v2, hipMemcpyHostToDevice);
     return upload_ctx(c, u0, v1, v2, hipMemcpyHostToDevice);
 }
 int mgx_upload_device(mgx_ctx *c, const double *u0, const double *v1, const double *v2) {
     if (c) c->bc_pending = false;
-    if (c) c->hist_valid = false;
+    if (c) c->hist_invalidate();
     if (c && c->dist) return dist_upload(c, u0, v1, v2, hipMemcpyDeviceToDevice);
     return upload_ctx(c, u0, v1, v2, hipMemcpyDeviceToDevice);
 }
@@ -1949,12 +1986,29 @@ int mgxi::sample_pieces(mgx_ctx *c, const std::vector<SamplePiece> &pieces, long
     if (!device_out) (void)hipFree(dst);
     return rc;
 }
+// fields 5 and 6, the history arrays h and h2 (level 0, and only while they
+// hold a time level): host-only, the flags of the context that owns them
+int mgxi::history_field_check(const mgx_ctx *c, int level, int field, const char *who) {
+    if (field != 5 && field != 6) return MGX_OK;
+    if (level != 0)
+        return fail(MGX_E_ARG, std::string(who) + ": the history is a finest-level array (fields "
+                                                  "5 and 6, level 0)");
+    if (field == 5 && !(c->hist_on && c->hist_valid))
+        return fail(MGX_E_ARG, std::string(who) + ": no valid history (field 5: "
+                                                  "mgx_set_history, then a step)");
+    if (field == 6 && !(c->hist2_on && c->hist2_valid))
+        return fail(MGX_E_ARG, std::string(who) + ": no valid second history array (field 6: "
+                                                  "mgx_set_history_depth(ctx, 2), then two steps)");
+    return MGX_OK;
+}
 // host-only argument check of (level, field) on a single-GPU context
 static int field_check(mgx_ctx *c, int level, int field, const char *who) {
     if (level < 0 || level >= c->L)
         return fail(MGX_E_ARG, std::string(who) + ": level out of range");
-    if (field < 0 || field > 4)
-        return fail(MGX_E_ARG, std::string(who) + ": field must be 0..4 (u, rhs, v1, v2, source)");
+    if (field < 0 || field > 6)
+        return fail(MGX_E_ARG, std::string(who) + ": field must be 0..6 (u, rhs, v1, v2, source, "
+                                                  "history, history2)");
+    CHK(history_field_check(c, level, field, who));
     if (field == 4 && level == 0 && c->src_terms)
         return fail(MGX_E_ARG, std::string(who) + ": the source is separable: no copy of it is "
                                                   "kept (field 4)");
@@ -1968,7 +2022,8 @@ int mgxi::field_view(mgx_ctx *c, int level, int field, mgxdiag::View *v) {
     HIPCHK(hipSetDevice(c->device));
     CHK(materialize(c, level));
     Level &L = c->lv[level];
-    v->a = field == 0 ? L.U() : field == 1 ? L.rhs : field == 2 ? L.v1 : field == 3 ? L.v2 : c->src;
+    v->a = field == 0 ? L.U() : field == 1 ? L.rhs : field == 2 ? L.v1 : field == 3 ? L.v2
+         : field == 4 ? c->src : field == 5 ? c->hist : c->hist2;
     v->row0 = 0;
     v->pitch = L.pitch;
     v->n = L.n;
@@ -2078,6 +2133,124 @@ int mgx_sample_rows(mgx_ctx *c, int part, int field, long stride, double *out, l
     *rows = c->N / stride + 1;
     if (!out) return MGX_OK;
     return sample_impl(c, 0, field, stride, out, false, "mgx_sample_rows");
+}
+
+}  // extern "C"
+
+// ---- the step error estimate (include/mgx.h "Step error estimate", csrc/errest.hip)
+int mgxi::step_error_view(mgx_ctx *c, const double *u, const double *h, const double *h2, long row0,
+                          long pitch, long n, long r0, long r1, double w, double atol, double rtol,
+                          mgx_step_err *out) {
+    mgxdiag::Rec *scr = nullptr;
+    CHK(diag_scratch(c, &scr));
+    mgxerr::Args A;
+    A.u = u;
+    A.h = h;
+    A.h2 = h2;
+    A.row0 = row0;
+    A.pitch = pitch;
+    A.n = n;
+    A.r0 = std::max<long>(r0, 1);   // the interior rows of [r0, r1)
+    A.r1 = std::max<long>(A.r0, std::min<long>(r1, n));
+    A.w = w;
+    A.p = 1.0 + w;
+    A.atol = atol;
+    A.rtol = rtol;
+    A.partials = reinterpret_cast<mgxerr::Rec *>(scr);
+    A.out = A.partials + mgxdiag::kMaxPartials;
+    mgxerr::PassTimer T;
+    T.begin(c->stream);
+    const bool ok = mgxerr::launch_step_error(A, c->stream);
+    T.end(c->stream);
+    if (!ok) return fail(MGX_E_ARG, "mgx_step_error: level too wide");
+    CHK(check_launch("step error estimate"));
+    mgxerr::Rec r;
+    HIPCHK(hipMemcpyAsync(&r, A.out, sizeof(r), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    mgxerr::to_step_err(r, n, A.r0, A.r1, w, out);
+    T.commit(24.0 * (double)out->count);
+    return MGX_OK;
+}
+// host-only checks shared by mgx_step_error and mgx_step_error_rows
+static int step_error_check(mgx_ctx *c, double atol, double rtol, mgx_step_err *out,
+                            const char *who) {
+    if (!c || !out) return fail(MGX_E_ARG, std::string(who) + ": null argument");
+    if (!mgxerr::tolerances_ok(atol, rtol))
+        return fail(MGX_E_ARG, std::string(who) + ": atol and rtol must be finite and >= 0, and "
+                                                  "not both zero");
+    if (!c->hist_on || !c->hist2_on)
+        return fail(MGX_E_ARG, std::string(who) + ": the context has no history of depth 2 "
+                                                  "(mgx_set_history_depth)");
+    if (!c->hist_valid || !c->hist2_valid)
+        return fail(MGX_E_ARG, std::string(who) + ": the history does not hold u^n and u^(n-1): "
+                                                  "two steps since the last upload or rollback "
+                                                  "give that");
+    return MGX_OK;
+}
+// the single-GPU context's three arrays: u by the route mgx_field_stats takes
+static int step_error_ctx(mgx_ctx *c, double w, double atol, double rtol, mgx_step_err *out) {
+    mgxdiag::View v;
+    CHK(field_view(c, 0, 0, &v));
+    return step_error_view(c, v.a, c->hist, c->hist2, 0, v.pitch, v.n, 0, v.n + 1, w, atol, rtol,
+                           out);
+}
+
+extern "C" {
+
+int mgx_step_error(mgx_ctx *c, double atol, double rtol, mgx_step_err *out) {
+    CHK(step_error_check(c, atol, rtol, out, "mgx_step_error"));
+    const double w = c->hist_dt / c->hist2_dt;
+    mgxerr::timer_reset();
+    if (c->dist) return dist_step_error(c, w, atol, rtol, out);
+    return step_error_ctx(c, w, atol, rtol, out);
+}
+int mgx_step_error_rows(mgx_ctx *c, int part, double atol, double rtol, mgx_step_err *out) {
+    CHK(step_error_check(c, atol, rtol, out, "mgx_step_error_rows"));
+    const double w = c->hist_dt / c->hist2_dt;
+    mgxerr::timer_reset();
+    if (c->dist) return dist_step_error_rows(c, part, w, atol, rtol, out, "mgx_step_error_rows");
+    if (part != 0)
+        return fail(MGX_E_ARG, "mgx_step_error_rows: a single-GPU context has part 0 only");
+    return step_error_ctx(c, w, atol, rtol, out);
+}
+int mgx_step_err_merge(mgx_step_err *into, const mgx_step_err *other) {
+    if (!into || !other) return fail(MGX_E_ARG, "mgx_step_err_merge: null argument");
+    if (!mgxerr::merge(into, *other))
+        return fail(MGX_E_ARG, "mgx_step_err_merge: the records' w differ: they are not of one "
+                               "step");
+    return MGX_OK;
+}
+int mgx_array_step_error(const double *u, const double *h, const double *h2, long n, double w,
+                         double atol, double rtol, mgx_step_err *out) {
+    if (!u || !h || !h2 || !out) return fail(MGX_E_ARG, "mgx_array_step_error: null argument");
+    if (n < 2) return fail(MGX_E_ARG, "mgx_array_step_error: n must be >= 2");
+    if (!mgxerr::tolerances_ok(atol, rtol))
+        return fail(MGX_E_ARG, "mgx_array_step_error: atol and rtol must be finite and >= 0, and "
+                               "not both zero");
+    if (!std::isfinite(w))
+        return fail(MGX_E_ARG, "mgx_array_step_error: w must be finite");
+    std::lock_guard<std::mutex> g(g_raw_mu);
+    int dev = 0;
+    HIPCHK(hipGetDevice(&dev));
+    static mgxerr::Rec *scr = nullptr;
+    static int scr_dev = -1;
+    if (!scr || scr_dev != dev) {
+        HIPCHK(hipMalloc(&scr, mgxdiag::scratch_bytes(1)));
+        scr_dev = dev;
+    }
+    mgxerr::timer_reset();
+    mgxerr::PassTimer T;
+    T.begin(nullptr);
+    const bool ok = mgxerr::launch_raw_step_error(u, h, h2, n, 1.0 + w, w, atol, rtol, scr,
+                                                  scr + mgxdiag::kMaxPartials, nullptr);
+    T.end(nullptr);
+    if (!ok) return fail(MGX_E_ARG, "mgx_array_step_error: n too large");
+    CHK(check_launch("mgx_array_step_error"));
+    mgxerr::Rec r;
+    HIPCHK(hipMemcpy(&r, scr + mgxdiag::kMaxPartials, sizeof(r), hipMemcpyDeviceToHost));
+    mgxerr::to_step_err(r, n, 1, n, w, out);
+    T.commit(24.0 * (double)out->count);
+    return MGX_OK;
 }
 
 }  // extern "C"
@@ -2374,6 +2547,13 @@ static int step_impl(mgx_ctx *c, double tol, int *cycles, bool prepare_next,
     double res0 = 0;
     if (c->k_bdf != 0) CHK(set_solve_k(c, 0.0));   // after mgx_step_bdf2
     if (c->hist_on) {   // mgx_set_history: h = u^n, before a pending ring is written
+        if (c->hist2_on) {   // depth 2: the copy goes into the older buffer
+            hist_swap(c);
+            c->hist2_valid = c->hist_valid;
+            c->hist2_dt = c->hist_dt;
+            c->hist_valid = false;   // (until the copy below is issued)
+        }
+        c->hist_rolled = false;
         CHK(c->dist ? dist_snapshot(c) : hist_snapshot_ctx(c));
         c->hist_dt = c->dt;
         c->hist_valid = true;
@@ -2462,8 +2642,58 @@ int mgx_set_history(mgx_ctx *c, int on) {
     else
         hist_free_ctx(c);
     c->hist_on = false;
-    c->hist_valid = false;
+    c->hist2_on = false;
+    c->hist_invalidate();
     c->hist_dt = 0;
+    c->hist2_dt = 0;
+    return MGX_OK;
+}
+int mgx_set_history_depth(mgx_ctx *c, int depth) {
+    if (!c) return fail(MGX_E_ARG, "mgx_set_history_depth: null ctx");
+    if (depth < 0 || depth > 2)
+        return fail(MGX_E_ARG, "mgx_set_history_depth: depth must be 0, 1 or 2");
+    const int have = c->hist_on ? (c->hist2_on ? 2 : 1) : 0;
+    if (depth == have) return MGX_OK;
+    if (depth == 0) return mgx_set_history(c, 0);
+    if (have == 0) CHK(mgx_set_history(c, 1));
+    if (depth == 1) {   // 2 -> 1: the older array goes
+        HIPCHK(hipSetDevice(c->device));
+        if (c->dist)
+            CHK(dist_set_history2(c, 0, false, "mgx_set_history_depth"));
+        else
+            hist2_free_ctx(c);
+        c->hist2_on = c->hist2_valid = false;   // (hist_rolled stays until the next step)
+        c->hist2_dt = 0;
+        return MGX_OK;
+    }
+    // -> 2, all parts or none; a failure leaves the depth the context had
+    HIPCHK(hipSetDevice(c->device));
+    const bool zero_hist = !c->hist_valid;
+    int rc;
+    if (c->dist) {
+        rc = dist_set_history2(c, 1, zero_hist, "mgx_set_history_depth");
+    } else {
+        rc = hist2_alloc_ctx(c, zero_hist, "mgx_set_history_depth");
+        if (rc != MGX_OK) hist2_free_ctx(c);
+    }
+    if (rc != MGX_OK) {
+        if (have == 0) {   // (mgx_set_history keeps the message of the failure intact)
+            const std::string msg = mgx_last_error();
+            (void)mgx_set_history(c, 0);
+            return fail(rc, msg);
+        }
+        return rc;
+    }
+    c->hist2_on = true;
+    c->hist2_valid = false;
+    c->hist2_dt = 0;
+    return MGX_OK;
+}
+int mgx_history_depth(mgx_ctx *c, int *depth, int *valid2, double *dt_prev2) {
+    if (!c) return fail(MGX_E_ARG, "mgx_history_depth: null ctx");
+    if (depth) *depth = c->hist_on ? (c->hist2_on ? 2 : 1) : 0;
+    if (valid2) *valid2 = c->hist2_valid ? 1 : 0;
+    if (dt_prev2) *dt_prev2 = c->hist2_dt;
     return MGX_OK;
 }
 int mgx_history_info(mgx_ctx *c, int *on, int *valid, double *dt_prev, double *k_solve) {
@@ -2488,6 +2718,14 @@ int mgx_step_bdf2(mgx_ctx *c, double tol, int *cycles, double *res0_out, double 
     drop_step_spec(c);
     // rhs, h <- u^n and mg_outer's initial norm in one pass
     double res0 = 0;
+    if (c->hist2_on) {
+        // depth 2: u^(n-1) is read where it lies and u^n stored into the older
+        // buffer -- no byte more than at depth 1
+        hist_swap(c);
+        c->hist2_valid = true;
+        c->hist2_dt = c->hist_dt;
+    }
+    c->hist_rolled = false;
     if (c->dist)
         CHK(dist_rhs_norm_bdf(c, K.b0, K.b1, cf, &res0));
     else
@@ -2509,12 +2747,24 @@ int mgx_rollback(mgx_ctx *c) {
     if (!c->hist_on || !c->hist_valid)
         return fail(MGX_E_ARG, "mgx_rollback: the context has no valid history (mgx_set_history, "
                                "then a step)");
+    if (c->hist_rolled)
+        return fail(MGX_E_ARG, "mgx_rollback: the step has been rolled back already: the history "
+                               "holds u^(n-1) for the next mgx_step_bdf2, not the u to go back to");
     HIPCHK(hipSetDevice(c->device));
     if (c->dist)
         CHK(dist_rollback(c));
     else
         CHK(hist_restore_ctx(c));
-    c->hist_valid = false;
+    if (c->hist2_on && c->hist2_valid) {
+        // depth 2: u^(n-1) and its dt become the history again, so the retry
+        // may be a BDF2 step at any dt
+        hist_swap(c);
+        c->hist_dt = c->hist2_dt;
+        c->hist2_valid = false;
+        c->hist_rolled = true;
+    } else {
+        c->hist_valid = false;
+    }
     HIPCHK(hipStreamSynchronize(c->stream));
     return MGX_OK;
 }
@@ -3079,6 +3329,14 @@ extern "C" int mgx_get_tuning(const char *key, long *value) {
         double us = 0, bytes = 0;
         mgxdiag::last_pass(&us, &bytes);
         *value = key[6] == 'u' ? (long)us : (long)bytes;
+        return MGX_OK;
+    }
+    // (read-only: the same of the calling thread's last error pass,
+    // mgx_step_error* / mgx_array_step_error)
+    if (!strcmp(key, "errest_us") || !strcmp(key, "errest_bytes")) {
+        double us = 0, bytes = 0;
+        mgxerr::last_pass(&us, &bytes);
+        *value = key[7] == 'u' ? (long)us : (long)bytes;
         return MGX_OK;
     }
     // (read-only: the device microseconds of the calling thread's last ring

@@ -372,6 +372,44 @@ class Multigrid:
         theta-step: call step() next."""
         check(lib().mgx_rollback(self._h))
 
+    # -- the step error estimate on a two-deep history (mgx_set_history_depth)
+    def set_history_depth(self, depth):
+        """mgx_set_history_depth: 0 = no history, 1 = set_history(), 2 = a
+        second array h2 beside h, so that after a step u^(n+1), u^n and u^(n-1)
+        are resident together -- what step_error() needs, and what lets
+        rollback() keep u^(n-1) for a BDF2 retry.  No data is copied for it.
+        Raises MGXError (MGX_E_HIP) where there is no room; the context then
+        keeps the depth it had."""
+        check(lib().mgx_set_history_depth(self._h, int(depth)))
+
+    def history_depth(self):
+        """-> dict(depth, valid2, dt_prev2) (mgx_history_depth): valid2 = h2
+        holds u^(n-1), dt_prev2 = the dt of the step that started from it."""
+        d, v2, dt2 = C.c_int(), C.c_int(), C.c_double()
+        check(lib().mgx_history_depth(self._h, C.byref(d), C.byref(v2), C.byref(dt2)))
+        return {"depth": d.value, "valid2": v2.value, "dt_prev2": dt2.value}
+
+    def step_error(self, atol, rtol):
+        """One reduction pass over u, h and h2 after a step (mgx_step_error) ->
+        StepError: with w = dt_prev / dt_prev2, at every interior point d = u -
+        ((1 + w) h - w h2), c = u - h and e = d / (atol + rtol max(|u|, |h|));
+        the sums of squares and the maxima of |e|, |d|, |c| over the points
+        with a finite e, where |e| is largest, and .rms of e.  Needs depth 2
+        and two steps since the last upload or rollback.  A local-parts solver
+        returns the parts' records merged in part order; an RCCL rank calls
+        step_error_rows and merges (step_err_merge)."""
+        s = _lib.StepErr()
+        check(lib().mgx_step_error(self._h, float(atol), float(rtol), C.byref(s)))
+        return _lib.StepError(s)
+
+    def step_error_rows(self, part, atol, rtol):
+        """step_error() of the owned finest-level rows of local part `part`,
+        with global positions and no communication (mgx_step_error_rows)."""
+        s = _lib.StepErr()
+        check(lib().mgx_step_error_rows(self._h, int(part), float(atol), float(rtol),
+                                        C.byref(s)))
+        return _lib.StepError(s)
+
     def velocity_factored(self):
         """mgx_velocity_factored: bit 0 = the finest level keeps velocity
         factors, bit l = level l generates its velocity from them."""
@@ -428,7 +466,9 @@ class Multigrid:
         return out
 
     # -- field diagnostics on the device (mgx_field_stats, mgx_sample)
-    _FIELDS = {"u": 0, "rhs": 1, "v1": 2, "v2": 3, "source": 4}
+    # ("history" / "history2": h and h2 of set_history / set_history_depth, level
+    # 0, while they hold a time level)
+    _FIELDS = {"u": 0, "rhs": 1, "v1": 2, "v2": 3, "source": 4, "history": 5, "history2": 6}
 
     def stats(self, field="u", level=0, interior=False, minus=None):
         """One reduction pass over what download_level(level, field) would

@@ -346,7 +346,7 @@ int mgx_get_tuning(const char *key, long *value);
  * profiles are stamped with) and of every product source (those + ctx.h,
  * plan.h, sepvel.h, mgx.hip, dist.hip, vfactor.h, vfactor.hip, source.h,
  * source.hip, diag.h, diag.hip, boundary.h, boundary.hip, tstep.h, tstep.hip,
- * bdf.h, bdf.hip, include/mgx.h). */
+ * bdf.h, bdf.hip, errest.h, errest.hip, include/mgx.h). */
 const char *mgx_build_id(void);
 const char *mgx_build_sources_id(void);
 
@@ -631,7 +631,10 @@ int mgx_array_stats(const double *a, const double *minus, long n, int interior_o
                     mgx_stats *out);
 /* The statistics of what mgx_download_level(level, field) would return, on the
  * context's stream.  field 0..3 as there, 4 = the context's copy of the source
- * (level 0; MGX_E_ARG when none is set).  minus: a device pointer in the
+ * (level 0; MGX_E_ARG when none is set), 5 = the history h and 6 = the second
+ * history array h2 (level 0; MGX_E_ARG when that array is absent or not valid
+ * -- mgx_set_history, mgx_set_history_depth; the only way to look at the
+ * history without a step).  minus: a device pointer in the
  * reference layout of that level, or NULL.  A local-parts context
  * (mgx_create_local_dist) takes level 0 only: the result is mgx_stats_merge of
  * its parts' owned-row results in part order (of sub-context 0 when every
@@ -889,6 +892,103 @@ int mgx_step_bdf2(mgx_ctx *ctx, double tol, int *cycles, double *res0, double *r
 int mgx_rollback(mgx_ctx *ctx);
 int mgx_compute_rhs_bdf2(double *rhs, const double *u, const double *h, long n, double b0,
                          double b1, const double *f, double c);
+
+/* ---- Step error estimate on a two-deep history --------------------------------
+ * An adaptive loop needs a measure of a step's error and a way back that does
+ * not lose second order.  mgx_set_history_depth(ctx, 2) gives the context a
+ * second history array h2 in the layout of h (one per part / sub-context, as
+ * h), so that after a step u = u^(n+1), h = u^n and h2 = u^(n-1) are resident
+ * together; mgx_step_error turns them into the record below in one reduction
+ * pass (csrc/errest.hip, part of mgx_build_sources_id).
+ *
+ * mgx_set_history_depth(ctx, depth): 0 = mgx_set_history(ctx, 0), 1 = the
+ * history of the section above, 2 = h and h2; anything else MGX_E_ARG.
+ * Allocation is all parts or none: on failure MGX_E_HIP with a message, and
+ * the context keeps the depth it had.  1 -> 2 keeps h and its validity, with
+ * valid2 = 0; 2 -> 1 frees h2.  mgx_set_history(ctx, 1) on a context that has a
+ * history leaves its depth alone, mgx_set_history(ctx, 0) frees everything.
+ * mgx_history_depth: the depth, whether h2 is valid, and dt_prev2, the dt of
+ * the step that started from h2.  Any pointer may be NULL.
+ *
+ * At depth 2 every mgx_step, mgx_step_ex and mgx_step_bdf2 ends with h = u^n
+ * as at depth 1 and h2 = what h held, valid2 = what valid was, dt_prev2 = what
+ * dt_prev was.  No data is copied for this: the step's snapshot is written into
+ * the older buffer and the two pointers are exchanged -- a theta-step's device
+ * copy goes into the old h2 buffer, and the BDF2 pass reads u^(n-1) from h and
+ * stores u^n into the other buffer, the bytes it moves at depth 1, where both
+ * pointers are the same address and the pass gives the same bits.  valid2 is
+ * cleared wherever valid is.  A context that never calls
+ * mgx_set_history_depth launches and returns exactly what it does without
+ * this section.
+ *
+ * mgx_rollback at depth 2: u = h as at depth 1, with the same drops.  Then, if
+ * valid2, the pointers are exchanged: h = u^(n-1), dt_prev = dt_prev2, valid
+ * stays 1, valid2 = 0 -- the retry may be mgx_step_bdf2 at any dt, second
+ * order.  Without valid2 it is the rollback of depth 1.  A second mgx_rollback
+ * before the next step is MGX_E_ARG: h is then not the u to go back to.
+ *
+ * The record.  All C doubles, every operation rounded, nothing contracted in
+ * either fp_mode, the division the true one.  On the host w = dt_prev /
+ * dt_prev2 and p = 1.0 + w.  At every interior point (rows and columns
+ * 1..n-1):
+ *     up = fl( fl(p*h) - fl(w*h2) )       linear extrapolation of u^(n-1), u^n
+ *                                         to t^(n+1)
+ *     d  = fl( u - up )
+ *     c  = fl( u - h )
+ *     sc = fl( atol + fl( rtol * max(|u|, |h|) ) )
+ *     e  = d / sc
+ * Conventions of mgx_stats: the sums are of fl(x*x), the maxima of |x|; for
+ * err_max the record gives the global position of the first occurrence in
+ * row-major order; the position is -1 and the three maxima are -Inf when no
+ * point is finite.  A point whose e is NaN or +-Inf counts in `nonfinite` and
+ * in nothing else (atol = 0 where u = h = 0 is such a point).  No
+ * floating-point atomics: the order of every addition is a fixed function of
+ * N and the row range, so two calls give the same bits.
+ *
+ * What d is: d = 1/2 dt (dt + dt_prev) u_tt + O(dt^3), with dt the step just
+ * taken.  Times w/(1+w) it is the textbook local error of an implicit-Euler
+ * step (theta = 1).  For the second-order steps (theta = 1/2, BDF2) it is a
+ * conservative curvature control, NOT their O(dt^3) local error: that would
+ * need a fourth time level, which is not kept.  c is the plain change of the
+ * step.  What a controller does with the record is the caller's business.
+ *
+ * mgx_step_error(ctx, atol, rtol, out): MGX_E_ARG before any device call, with
+ * a message that starts with the function's name, for a NULL argument, atol or
+ * rtol not finite, negative or both zero, a context that is not at depth 2, and
+ * a history without valid and valid2 (two steps since the last upload give
+ * that; a rollback takes it away).  Single-GPU and local-parts contexts take it;
+ * a local-parts context returns mgx_step_err_merge of its parts' owned-row
+ * records in part order (of sub-context 0 when every level is replicated).  An
+ * RCCL rank returns MGX_E_ARG -- the call communicates nothing -- and calls
+ * mgx_step_error_rows (the owned rows of local part `part`; any context, a
+ * single-GPU context has part 0) and merges.  u is read by the route
+ * mgx_field_stats takes; pending and speculative state is left alone.
+ * mgx_step_err_merge, host only: counts and sums add, the maxima by value,
+ * err_max ties to the smaller (i, j); a record without a finite point leaves
+ * the other's maxima alone; MGX_E_ARG (nothing changed) when the records' w
+ * differ.
+ * Raw op mgx_array_step_error: device pointers, reference layout, any n >= 2,
+ * null stream; synchronises.  w finite.
+ * Accounting: compulsory bytes 24 per interior point; the read-only tuning keys
+ * "errest_us" / "errest_bytes" (mgx_get_tuning) give the device microseconds and
+ * bytes of the calling thread's last call, as "stats_us" / "stats_bytes" do.
+ * Measured at N=16384 on one MI355X: DESIGN.md section 14. */
+typedef struct mgx_step_err {
+    long   count;        /* interior points examined */
+    long   nonfinite;    /* points whose e is NaN or +-Inf; excluded from everything below */
+    double w;            /* dt_prev / dt_prev2, as used */
+    double err_sum_sq, err_max;   /* e */
+    long   err_max_i, err_max_j;
+    double d_sum_sq, d_max;       /* d */
+    double c_sum_sq, c_max;       /* c */
+} mgx_step_err;
+int mgx_set_history_depth(mgx_ctx *ctx, int depth);
+int mgx_history_depth(mgx_ctx *ctx, int *depth, int *valid2, double *dt_prev2);
+int mgx_step_error(mgx_ctx *ctx, double atol, double rtol, mgx_step_err *out);
+int mgx_step_error_rows(mgx_ctx *ctx, int part, double atol, double rtol, mgx_step_err *out);
+int mgx_step_err_merge(mgx_step_err *into, const mgx_step_err *other);
+int mgx_array_step_error(const double *u, const double *h, const double *h2, long n, double w,
+                         double atol, double rtol, mgx_step_err *out);
 
 #ifdef __cplusplus
 }
