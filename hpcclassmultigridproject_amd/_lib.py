@@ -196,6 +196,13 @@ _SIGS = {
     "mgx_step_error_rows": (_I, [_vp, _I, _D, _D, C.POINTER(StepErr)]),
     "mgx_step_err_merge": (_I, [C.POINTER(StepErr), C.POINTER(StepErr)]),
     "mgx_array_step_error": (_I, [_vp, _vp, _vp, _L, _D, _D, _D, C.POINTER(StepErr)]),
+    "mgx_dense_weights": (_I, [_I, _D, _D, _D, _dp, _dp, _dp]),
+    "mgx_dense_output": (_I, [_vp, _I, _D, _L, _vp]),
+    "mgx_dense_output_device": (_I, [_vp, _I, _D, _L, _vp]),
+    "mgx_dense_output_rows": (_I, [_vp, _I, _I, _D, _L, _vp, C.POINTER(_L), C.POINTER(_L)]),
+    "mgx_dense_points": (_I, [_vp, _I, _D, _L, _vp, _vp, _vp]),
+    "mgx_dense_points_device": (_I, [_vp, _I, _D, _L, _vp, _vp, _vp]),
+    "mgx_array_dense": (_I, [_vp, _vp, _vp, _vp, _L, _D, _D, _D, _I]),
     "mgx_build_id": (C.c_char_p, []),
     "mgx_build_sources_id": (C.c_char_p, []),
 }
@@ -386,6 +393,39 @@ def next_dt(dt, err, order, safety=0.9, fmin=0.2, fmax=2.0):
     if err == 0.0:
         return dt * fmax
     return dt * min(fmax, max(fmin, safety * abs(err) ** (-1.0 / order)))
+
+
+def dense_weights(order, tau, dt1, dt2=0.0):
+    """mgx_dense_weights -> (w0, w1, w2): the weights of the interpolant of the
+    given order (0: u alone, 1: linear through u and h, 2: the Lagrange
+    quadratic through u, h and h2) at tau = t* - t^(n+1) <= 0, after steps dt1
+    (the last) and dt2 (the one before); host only, each operation rounded."""
+    w0, w1, w2 = C.c_double(), C.c_double(), C.c_double()
+    check(lib().mgx_dense_weights(int(order), float(tau), float(dt1), float(dt2), C.byref(w0),
+                                  C.byref(w1), C.byref(w2)))
+    return w0.value, w1.value, w2.value
+
+
+def array_dense(out, u, h, h2, n, w0, w1, w2, levels):
+    """mgx_array_dense: out = the point formula of dense output on device
+    arrays in the reference layout ((n+1)^2 float64, any n >= 1): levels 1 out
+    = u, 2 out = fl(fl(w0 u) + fl(w1 h)), 3 that + fl(w2 h2).  h, h2: None
+    where `levels` does not read them.  Null stream; synchronises."""
+    cnt = (n + 1) * (n + 1)
+    check(lib().mgx_array_dense(device_ptr(out, cnt, "out"), device_ptr(u, cnt, "u"),
+                                device_ptr(h, cnt, "h"), device_ptr(h2, cnt, "h2"), n,
+                                float(w0), float(w1), float(w2), int(levels)))
+    return out
+
+
+def outputs_between(t_old, t_new, t_eval):
+    """The entries of a sorted t_eval that lie in (t_old, t_new], the interval
+    of an accepted step, as (index, tau) pairs with tau = t_eval[index] - t_new
+    <= 0: what Multigrid.dense takes after that step (host only)."""
+    import bisect
+    lo = bisect.bisect_right(t_eval, t_old)
+    hi = bisect.bisect_right(t_eval, t_new)
+    return [(k, t_eval[k] - t_new) for k in range(lo, hi)]
 
 
 def factor_velocity_device(v, n, ld=None, smin=0.0):

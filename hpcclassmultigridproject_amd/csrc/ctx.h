@@ -9,6 +9,7 @@
 
 #include "../../include/mgx.h"
 #include "boundary.h"
+#include "dense.h"
 #include "diag.h"
 #include "kernels.h"
 
@@ -150,6 +151,10 @@ struct mgx_ctx {
     // scratch of the field diagnostics (diag.h: partial records + the result),
     // allocated by the first statistics call
     void *diag = nullptr;
+    // staging of mgx_dense_points (csrc/dense.h): 2 * dense_cap indices (long)
+    // followed by dense_cap values, grown on demand
+    void *dense_buf = nullptr;
+    long dense_cap = 0;
     // mgx_set_boundary: two rings of 4(N+1) doubles, allocated by the first
     // call that needs one -- [0] the pending ring of MGX_BC_NEXT_STEP
     // (bc_pending: the next mgx_step consumes it), [1] the staging of a host
@@ -325,6 +330,37 @@ int step_error_view(mgx_ctx *c, const double *u, const double *h, const double *
 int dist_step_error_rows(mgx_ctx *c, int part, double w, double atol, double rtol,
                          mgx_step_err *out, const char *who);
 int dist_step_error(mgx_ctx *c, double w, double atol, double rtol, mgx_step_err *out);
+// tuning key "dense_store" (mgx.hip): how the dense march stores out (dense.h)
+extern long g_dense_store;
+extern long g_dense_rows;   // tuning key "dense_rows"
+// Dense output (csrc/dense.h; mgx.hip), shared with dist.hip.  A piece: the
+// arrays of one part (Src with the weights set) and the sampled rows A in [A0,
+// A1) it writes (fine rows A * stride; stride 1: the rows themselves).
+struct DensePiece {
+    mgxdense::Src s;
+    long A0 = 0, A1 = 0;
+};
+// out[(A - A0) * (n/stride + 1) + B] for the pieces' rows, `rows` rows in all:
+// the march (stride 1) or the gather into a compact device buffer that is
+// copied once (host out), or into out itself (device out).  Synchronises.
+int dense_pieces(mgx_ctx *c, const std::vector<DensePiece> &pieces, long stride, long A0,
+                 long rows, double *out, bool device_out);
+// A piece of the point probes: the rows [A0, A1) are the rows the arrays hold
+// and answer for.  pi, pj, out: device; fill_unheld: a valid point in no piece's
+// rows gives NaN.  Synchronises.
+int dense_points_pieces(mgx_ctx *c, const std::vector<DensePiece> &pieces, bool fill_unheld,
+                        long npts, const long *pi, const long *pj, double *out);
+// the single-GPU context's arrays (u by field_view's route) with the weights w
+int dense_src_ctx(mgx_ctx *c, int levels, const double w[3], mgxdense::Src *s);
+// ... on a partitioned context (dist.hip); `who` names the C entry point
+int dist_dense(mgx_ctx *c, int levels, const double w[3], long stride, double *out,
+               bool device_out, const char *who);
+int dist_dense_rows(mgx_ctx *c, int part, int levels, const double w[3], long stride, double *out,
+                    long *first_row, long *rows, const char *who);
+// the points of every local part's owned rows (of sub-context 0 where every
+// level is replicated); device pointers.  An RCCL rank's other rows give NaN.
+int dist_dense_points(mgx_ctx *c, int levels, const double w[3], long npts, const long *pi,
+                      const long *pj, double *out);
 int dist_snapshot(mgx_ctx *c);
 int dist_rhs_norm_bdf(mgx_ctx *c, double b0, double b1, double cf, double *res0);
 int dist_rollback(mgx_ctx *c);

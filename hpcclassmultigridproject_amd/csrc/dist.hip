@@ -39,6 +39,7 @@
 #include "tstep.h"
 #include "bdf.h"
 #include "errest.h"
+#include "dense.h"
 
 namespace mgxi {
 
@@ -1984,6 +1985,100 @@ int dist_sample_rows(mgx_ctx *c, int part, int field, long stride, double *out, 
     CHK(settle(c));
     CHK(part_view(c, part, field, who, &s.f, &ra, &rb));
     return sample_pieces(c, {s}, stride, s.A0, *rows, out, false);
+}
+
+// ---------------------------------------------------------------- dense output
+// The arrays of local part `from` (u by part_view's route, the part's history
+// arrays beside it: one layout) with the weights w, as step_error_part reads them
+static int dense_src(mgx_ctx *c, int from, int levels, const double w[3], const char *who,
+                     mgxdense::Src *s) {
+    Dist *d = c->dist;
+    mgxdiag::View v;
+    int ra, rb;
+    CHK(part_view(c, from, 0, who, &v, &ra, &rb));
+    const double *h, *h2;
+    if (d->la == 0) {
+        h = d->parts[from].sub->hist;
+        h2 = d->parts[from].sub->hist2;
+    } else {
+        h = d->parts[from].lv[0].hist;
+        h2 = d->parts[from].lv[0].hist2;
+    }
+    s->u = v.a;
+    s->h = levels >= 2 ? h : nullptr;
+    s->h2 = levels >= 3 ? h2 : nullptr;
+    s->row0 = v.row0;
+    s->pitch = v.pitch;
+    s->n = v.n;
+    s->levels = levels;
+    s->w0 = w[0];
+    s->w1 = w[1];
+    s->w2 = w[2];
+    return MGX_OK;
+}
+// mgx_dense_output[_device]: dist_sample's pieces
+int dist_dense(mgx_ctx *c, int levels, const double w[3], long stride, double *out,
+               bool device_out, const char *who) {
+    Dist *d = c->dist;
+    if (!d->local)
+        return fail(MGX_E_ARG, std::string(who) + ": an RCCL rank holds its own rows and this "
+                                                  "call does not communicate: use "
+                                                  "mgx_dense_output_rows");
+    HIPCHK(hipSetDevice(c->device));
+    CHK(settle(c));
+    std::vector<DensePiece> ps;
+    const int np = d->la == 0 ? 1 : (int)d->parts.size();
+    for (int p = 0; p < np; ++p) {
+        DensePiece s;
+        int ra, rb;
+        CHK(dense_src(c, p, levels, w, who, &s.s));
+        plan_rows(c->N, 0, d->world, d->parts[p].rank, &ra, &rb);
+        if (d->la == 0) {
+            ra = 0;
+            rb = (int)c->N + 1;
+        }
+        sampled_rows(ra, rb, stride, &s.A0, &s.A1);
+        ps.push_back(s);
+    }
+    return dense_pieces(c, ps, stride, 0, c->N / stride + 1, out, device_out);
+}
+// mgx_dense_output_rows: dist_sample_rows
+int dist_dense_rows(mgx_ctx *c, int part, int levels, const double w[3], long stride, double *out,
+                    long *first_row, long *rows, const char *who) {
+    Dist *d = c->dist;
+    if (part < 0 || part >= (int)d->parts.size())
+        return fail(MGX_E_ARG, std::string(who) + ": bad part");
+    DensePiece s;
+    int ra, rb;
+    plan_rows(c->N, 0, d->world, d->parts[part].rank, &ra, &rb);
+    sampled_rows(ra, rb, stride, &s.A0, &s.A1);
+    *first_row = s.A0 * stride;
+    *rows = std::max<long>(0, s.A1 - s.A0);
+    if (!out || *rows == 0) return MGX_OK;
+    HIPCHK(hipSetDevice(c->device));
+    CHK(settle(c));
+    CHK(dense_src(c, part, levels, w, who, &s.s));
+    return dense_pieces(c, {s}, stride, s.A0, *rows, out, false);
+}
+int dist_dense_points(mgx_ctx *c, int levels, const double w[3], long npts, const long *pi,
+                      const long *pj, double *out) {
+    Dist *d = c->dist;
+    const char *who = "mgx_dense_points";
+    HIPCHK(hipSetDevice(c->device));
+    CHK(settle(c));
+    std::vector<DensePiece> ps;
+    for (int p = 0; p < (int)d->parts.size(); ++p) {
+        DensePiece s;
+        int ra, rb;
+        // every level replicated: sub-context 0 holds the grid
+        CHK(dense_src(c, d->la == 0 ? 0 : p, levels, w, who, &s.s));
+        plan_rows(c->N, 0, d->world, d->parts[p].rank, &ra, &rb);
+        s.A0 = ra;
+        s.A1 = rb;
+        ps.push_back(s);
+    }
+    // local parts cover every row; an RCCL rank's other rows give NaN
+    return dense_points_pieces(c, ps, !d->local, npts, pi, pj, out);
 }
 
 // Row-block upload, correct tower: which partitioned coarse levels generate

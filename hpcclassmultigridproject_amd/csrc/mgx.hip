@@ -24,6 +24,7 @@
 #include "tstep.h"
 #include "bdf.h"
 #include "errest.h"
+#include "dense.h"
 #include "vfactor.h"
 
 namespace mgxi {
@@ -1361,6 +1362,7 @@ void free_ctx(mgx_ctx *c) {
     (void)hipFree(c->src_a);
     (void)hipFree(c->src_b);
     (void)hipFree(c->diag);
+    (void)hipFree(c->dense_buf);
     (void)hipFree(c->bc_buf);
     (void)hipFree(c->hist);
     (void)hipFree(c->hist2);
@@ -2250,6 +2252,257 @@ int mgx_array_step_error(const double *u, const double *h, const double *h2, lon
     HIPCHK(hipMemcpy(&r, scr + mgxdiag::kMaxPartials, sizeof(r), hipMemcpyDeviceToHost));
     mgxerr::to_step_err(r, n, 1, n, w, out);
     T.commit(24.0 * (double)out->count);
+    return MGX_OK;
+}
+
+}  // extern "C"
+
+// ---- dense output (include/mgx.h "Dense output", csrc/dense.hip)
+// tuning key "dense_store": how the stride-1 march stores out (dense.h)
+long mgxi::g_dense_store = 0;
+// tuning key "dense_rows": the rows of a workgroup of that march (0: the row
+// groups of the error pass; 4, one batch of loads, measured fastest: DESIGN 15)
+long mgxi::g_dense_rows = 4;
+
+int mgxi::dense_pieces(mgx_ctx *c, const std::vector<DensePiece> &pieces, long stride, long A0,
+                       long rows, double *out, bool device_out) {
+    if (rows <= 0) return MGX_OK;
+    const long cols = pieces[0].s.n / stride + 1;
+    const size_t bytes = sizeof(double) * (size_t)rows * (size_t)cols;
+    double *dst = out;
+    if (!device_out) HIPCHK(hipMalloc(&dst, bytes));
+    int rc = MGX_OK;
+    long pts = 0;
+    mgxdense::PassTimer T;
+    T.begin(c->stream);
+    for (const DensePiece &p : pieces) {
+        if (stride == 1)
+            mgxdense::launch_march(p.s, p.A0, p.A1, dst, A0, (int)g_dense_store,
+                                   (int)g_dense_rows, c->stream);
+        else
+            mgxdense::launch_gather(p.s, stride, p.A0, p.A1, dst + (p.A0 - A0) * cols, cols,
+                                    c->stream);
+        pts += std::max<long>(0, p.A1 - p.A0) * cols;
+        if ((rc = check_launch("dense output")) != MGX_OK) break;
+    }
+    T.end(c->stream);
+    if (rc == MGX_OK && !device_out &&
+        hipMemcpyAsync(out, dst, bytes, hipMemcpyDeviceToHost, c->stream) != hipSuccess)
+        rc = fail(MGX_E_HIP, "dense output: copy");
+    if (hipStreamSynchronize(c->stream) != hipSuccess && rc == MGX_OK)
+        rc = fail(MGX_E_HIP, "dense output: sync");
+    if (!device_out) (void)hipFree(dst);
+    if (rc == MGX_OK) T.commit(8.0 * (pieces[0].s.levels + 1) * (double)pts);
+    return rc;
+}
+int mgxi::dense_points_pieces(mgx_ctx *c, const std::vector<DensePiece> &pieces, bool fill_unheld,
+                              long npts, const long *pi, const long *pj, double *out) {
+    mgxdense::PassTimer T;
+    T.begin(c->stream);
+    // (stream order: the first launch fills what no piece holds, the later ones
+    // write their own rows only)
+    for (size_t k = 0; k < pieces.size(); ++k) {
+        const DensePiece &p = pieces[k];
+        mgxdense::launch_points(p.s, p.A0, p.A1, fill_unheld && k == 0, npts, pi, pj, out,
+                                c->stream);
+        CHK(check_launch("dense points"));
+    }
+    T.end(c->stream);
+    HIPCHK(hipStreamSynchronize(c->stream));
+    T.commit(8.0 * (pieces[0].s.levels + 1) * (double)npts);
+    return MGX_OK;
+}
+int mgxi::dense_src_ctx(mgx_ctx *c, int levels, const double w[3], mgxdense::Src *s) {
+    mgxdiag::View v;
+    CHK(field_view(c, 0, 0, &v));
+    s->u = v.a;
+    s->h = levels >= 2 ? c->hist : nullptr;
+    s->h2 = levels >= 3 ? c->hist2 : nullptr;
+    s->row0 = v.row0;
+    s->pitch = v.pitch;
+    s->n = v.n;
+    s->levels = levels;
+    s->w0 = w[0];
+    s->w1 = w[1];
+    s->w2 = w[2];
+    return MGX_OK;
+}
+// host-only checks shared by the context's dense calls, and the weights from
+// the history's own step sizes (not the context's current dt)
+static int dense_check(mgx_ctx *c, int order, double tau, const char *who, double w[3]) {
+    if (!c) return fail(MGX_E_ARG, std::string(who) + ": null ctx");
+    if (order < 0 || order > 2)
+        return fail(MGX_E_ARG, std::string(who) + ": order must be 0, 1 or 2");
+    if (!std::isfinite(tau)) return fail(MGX_E_ARG, std::string(who) + ": tau must be finite");
+    if (order >= 1 && !(c->hist_on && c->hist_valid))
+        return fail(MGX_E_ARG, std::string(who) + ": order >= 1 needs a valid history "
+                                                  "(mgx_set_history, then a step)");
+    if (order == 2 && !(c->hist2_on && c->hist2_valid))
+        return fail(MGX_E_ARG, std::string(who) + ": order 2 needs a history of depth 2 that holds "
+                                                  "u^n and u^(n-1) (mgx_set_history_depth(ctx, "
+                                                  "2), then two steps)");
+    if (mgxdense::weights(order, tau, c->hist_dt, c->hist2_dt, w) != 0)
+        return fail(MGX_E_ARG, std::string(who) + ": the history's step sizes are not positive");
+    return MGX_OK;
+}
+static int dense_stride_check(long n, long stride, const char *who) {
+    if (stride < 1 || stride > n || n % stride)
+        return fail(MGX_E_ARG, std::string(who) + ": stride must divide N (1 <= stride <= N)");
+    return MGX_OK;
+}
+static int dense_output_impl(mgx_ctx *c, int order, double tau, long stride, double *out,
+                             bool device_out, const char *who) {
+    double w[3];
+    CHK(dense_check(c, order, tau, who, w));
+    if (!out) return fail(MGX_E_ARG, std::string(who) + ": null out");
+    CHK(dense_stride_check(c->N, stride, who));
+    mgxdense::timer_reset();
+    if (c->dist) return dist_dense(c, order + 1, w, stride, out, device_out, who);
+    DensePiece p;
+    CHK(dense_src_ctx(c, order + 1, w, &p.s));
+    p.A0 = 0;
+    p.A1 = c->N / stride + 1;
+    return dense_pieces(c, {p}, stride, 0, p.A1, out, device_out);
+}
+// the context's staging of mgx_dense_points: room for npts points
+static int dense_staging(mgx_ctx *c, long npts, long **pi, long **pj, double **val) {
+    if (npts > c->dense_cap) {
+        const long cap = std::max<long>(1024, std::max(npts, 2 * c->dense_cap));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        (void)hipFree(c->dense_buf);
+        c->dense_buf = nullptr;
+        c->dense_cap = 0;
+        HIPCHK(hipMalloc(&c->dense_buf, 24 * (size_t)cap));
+        c->dense_cap = cap;
+    }
+    *pi = static_cast<long *>(c->dense_buf);
+    *pj = *pi + c->dense_cap;
+    *val = reinterpret_cast<double *>(*pj + c->dense_cap);
+    return MGX_OK;
+}
+static int dense_points_launch(mgx_ctx *c, int levels, const double w[3], long npts,
+                               const long *pi, const long *pj, double *out) {
+    if (c->dist) return dist_dense_points(c, levels, w, npts, pi, pj, out);
+    DensePiece p;
+    CHK(dense_src_ctx(c, levels, w, &p.s));
+    p.A0 = 0;
+    p.A1 = c->N + 1;
+    return dense_points_pieces(c, {p}, true, npts, pi, pj, out);
+}
+
+extern "C" {
+
+int mgx_dense_weights(int order, double tau, double dt1, double dt2, double *w0, double *w1,
+                      double *w2) {
+    double w[3];
+    switch (mgxdense::weights(order, tau, dt1, dt2, w)) {
+    case 0: break;
+    case 1: return fail(MGX_E_ARG, "mgx_dense_weights: order must be 0, 1 or 2");
+    case 2: return fail(MGX_E_ARG, "mgx_dense_weights: tau must be finite");
+    case 3: return fail(MGX_E_ARG, "mgx_dense_weights: dt1 must be finite and > 0 (order >= 1)");
+    default: return fail(MGX_E_ARG, "mgx_dense_weights: dt2 must be finite and > 0 (order 2)");
+    }
+    if (w0) *w0 = w[0];
+    if (w1) *w1 = w[1];
+    if (w2) *w2 = w[2];
+    return MGX_OK;
+}
+int mgx_dense_output(mgx_ctx *c, int order, double tau, long stride, double *out) {
+    return dense_output_impl(c, order, tau, stride, out, false, "mgx_dense_output");
+}
+int mgx_dense_output_device(mgx_ctx *c, int order, double tau, long stride, double *out) {
+    return dense_output_impl(c, order, tau, stride, out, true, "mgx_dense_output_device");
+}
+int mgx_dense_output_rows(mgx_ctx *c, int part, int order, double tau, long stride, double *out,
+                          long *first_row, long *rows) {
+    const char *who = "mgx_dense_output_rows";
+    double w[3];
+    CHK(dense_check(c, order, tau, who, w));
+    if (!first_row || !rows) return fail(MGX_E_ARG, std::string(who) + ": null argument");
+    CHK(dense_stride_check(c->N, stride, who));
+    mgxdense::timer_reset();
+    if (c->dist) return dist_dense_rows(c, part, order + 1, w, stride, out, first_row, rows, who);
+    if (part != 0) return fail(MGX_E_ARG, std::string(who) + ": a single-GPU context has part 0 only");
+    *first_row = 0;
+    *rows = c->N / stride + 1;
+    if (!out) return MGX_OK;
+    DensePiece p;
+    CHK(dense_src_ctx(c, order + 1, w, &p.s));
+    p.A0 = 0;
+    p.A1 = *rows;
+    return dense_pieces(c, {p}, stride, 0, p.A1, out, false);
+}
+int mgx_dense_points(mgx_ctx *c, int order, double tau, long npts, const long *pi, const long *pj,
+                     double *out) {
+    const char *who = "mgx_dense_points";
+    double w[3];
+    CHK(dense_check(c, order, tau, who, w));
+    if (npts < 0) return fail(MGX_E_ARG, std::string(who) + ": npts must be >= 0");
+    if (npts > 0 && (!pi || !pj || !out))
+        return fail(MGX_E_ARG, std::string(who) + ": null argument");
+    mgxdense::timer_reset();
+    if (npts == 0) return MGX_OK;
+    // every index inside the grid, and in a row this context holds
+    std::vector<std::pair<long, long>> held;
+    if (c->dist) {
+        for (int p = 0; p < dist_nsub(c); ++p) {
+            int ra, rb;
+            CHK(dist_owned_rows(c, p, &ra, &rb));
+            held.push_back({ra, rb});
+        }
+    } else {
+        held.push_back({0, c->N + 1});
+    }
+    for (long k = 0; k < npts; ++k) {
+        if (pi[k] < 0 || pi[k] > c->N || pj[k] < 0 || pj[k] > c->N)
+            return fail(MGX_E_ARG, std::string(who) + ": point k = " + std::to_string(k) +
+                                       " lies outside the grid (0 <= pi, pj <= N)");
+        bool ok = false;
+        for (const auto &r : held) ok = ok || (pi[k] >= r.first && pi[k] < r.second);
+        if (!ok)
+            return fail(MGX_E_ARG, std::string(who) + ": point k = " + std::to_string(k) +
+                                       " lies in a row this rank does not own");
+    }
+    HIPCHK(hipSetDevice(c->device));
+    long *di, *dj;
+    double *dv;
+    CHK(dense_staging(c, npts, &di, &dj, &dv));
+    HIPCHK(hipMemcpyAsync(di, pi, sizeof(long) * (size_t)npts, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(dj, pj, sizeof(long) * (size_t)npts, hipMemcpyHostToDevice, c->stream));
+    CHK(dense_points_launch(c, order + 1, w, npts, di, dj, dv));
+    HIPCHK(hipMemcpyAsync(out, dv, sizeof(double) * (size_t)npts, hipMemcpyDeviceToHost,
+                          c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return MGX_OK;
+}
+int mgx_dense_points_device(mgx_ctx *c, int order, double tau, long npts, const long *pi,
+                            const long *pj, double *out) {
+    const char *who = "mgx_dense_points_device";
+    double w[3];
+    CHK(dense_check(c, order, tau, who, w));
+    if (npts < 0) return fail(MGX_E_ARG, std::string(who) + ": npts must be >= 0");
+    if (npts > 0 && (!pi || !pj || !out))
+        return fail(MGX_E_ARG, std::string(who) + ": null argument");
+    mgxdense::timer_reset();
+    if (npts == 0) return MGX_OK;
+    HIPCHK(hipSetDevice(c->device));
+    return dense_points_launch(c, order + 1, w, npts, pi, pj, out);
+}
+int mgx_array_dense(double *out, const double *u, const double *h, const double *h2, long n,
+                    double w0, double w1, double w2, int levels) {
+    if (levels < 1 || levels > 3)
+        return fail(MGX_E_ARG, "mgx_array_dense: levels must be 1, 2 or 3");
+    if (!out || !u || (levels >= 2 && !h) || (levels >= 3 && !h2))
+        return fail(MGX_E_ARG, "mgx_array_dense: null argument");
+    if (n < 1) return fail(MGX_E_ARG, "mgx_array_dense: n must be >= 1");
+    mgxdense::timer_reset();
+    mgxdense::PassTimer T;
+    T.begin(nullptr);
+    mgxdense::launch_raw(out, u, h, h2, n, w0, w1, w2, levels, nullptr);
+    T.end(nullptr);
+    CHK(check_launch("mgx_array_dense"));
+    HIPCHK(hipStreamSynchronize(nullptr));
+    T.commit(8.0 * (levels + 1) * (double)(n + 1) * (double)(n + 1));
     return MGX_OK;
 }
 
@@ -3194,6 +3447,16 @@ extern "C" int mgx_set_tuning(const char *key, long value) {
         mgxi::g_source_sv = value;
         return MGX_OK;
     }
+    if (!strcmp(key, "dense_rows")) {
+        if (value < 0 || value > 65535) return fail(MGX_E_ARG, "dense_rows must be 0..65535");
+        mgxi::g_dense_rows = value;
+        return MGX_OK;
+    }
+    if (!strcmp(key, "dense_store")) {
+        if (value < 0 || value > 2) return fail(MGX_E_ARG, "dense_store must be 0, 1 or 2");
+        mgxi::g_dense_store = value;
+        return MGX_OK;
+    }
     if (!strcmp(key, "zero_rows")) {
         if (value != 0 && value != 1) return fail(MGX_E_ARG, "zero_rows must be 0 or 1");
         mgxi::g_zero_rows = value;
@@ -3337,6 +3600,22 @@ extern "C" int mgx_get_tuning(const char *key, long *value) {
         double us = 0, bytes = 0;
         mgxerr::last_pass(&us, &bytes);
         *value = key[7] == 'u' ? (long)us : (long)bytes;
+        return MGX_OK;
+    }
+    // (read-only: the same of the calling thread's last dense call,
+    // mgx_dense_output* / mgx_dense_points* / mgx_array_dense)
+    if (!strcmp(key, "dense_us") || !strcmp(key, "dense_bytes")) {
+        double us = 0, bytes = 0;
+        mgxdense::last_pass(&us, &bytes);
+        *value = key[6] == 'u' ? (long)us : (long)bytes;
+        return MGX_OK;
+    }
+    if (!strcmp(key, "dense_rows")) {
+        *value = mgxi::g_dense_rows;
+        return MGX_OK;
+    }
+    if (!strcmp(key, "dense_store")) {
+        *value = mgxi::g_dense_store;
         return MGX_OK;
     }
     // (read-only: the device microseconds of the calling thread's last ring

@@ -533,6 +533,69 @@ class Multigrid:
                                         C.byref(rows)))
         return first.value, out
 
+    # -- dense output (mgx_dense_output, mgx_dense_points)
+    def dense(self, order, tau, stride=1, out=None):
+        """The interpolant through the resident time levels at tau = t* -
+        t^(n+1) <= 0, every stride-th row and column -> an (m+1, m+1) array, m =
+        N/stride (mgx_dense_output): order 0 = u, 1 = linear through u and the
+        history h, 2 = the quadratic through u, h and h2 (depth 2, two steps),
+        with the weights dense_weights(order, tau, dt_prev, dt_prev2).  stride 1
+        is the whole field.  out: a numpy array, or a device tensor the kernel
+        writes directly.  An RCCL rank calls dense_rows."""
+        if stride < 1 or self.N % stride:
+            raise _lib.MGXError(_lib.MGX_E_ARG, "dense: stride must divide N")
+        m = self.N // stride
+        if out is not None and not isinstance(out, np.ndarray):
+            check(lib().mgx_dense_output_device(self._h, int(order), float(tau), stride,
+                                                _lib.device_ptr(out, (m + 1) ** 2, "out")))
+            return out
+        out = np.empty((m + 1, m + 1), dtype=np.float64) if out is None else out
+        if out.size != (m + 1) ** 2:
+            raise ValueError(f"out must hold {(m + 1) ** 2} doubles")
+        check(lib().mgx_dense_output(self._h, int(order), float(tau), stride, _np_ptr(out)))
+        return out
+
+    def dense_rows(self, part, order, tau, stride=1):
+        """-> (first_row, array): dense() of the sampled rows i (i % stride ==
+        0) among the owned rows of local part `part`, rows x (N/stride+1), with
+        no communication (mgx_dense_output_rows)."""
+        first, rows = C.c_long(), C.c_long()
+        args = (self._h, int(part), int(order), float(tau), stride)
+        check(lib().mgx_dense_output_rows(*args, None, C.byref(first), C.byref(rows)))
+        out = np.empty((rows.value, self.N // stride + 1), dtype=np.float64)
+        if rows.value:
+            check(lib().mgx_dense_output_rows(*args, _np_ptr(out), C.byref(first),
+                                              C.byref(rows)))
+        return first.value, out
+
+    def dense_points(self, order, tau, i, j, out=None):
+        """The interpolant at the grid points (i[k], j[k]) -> one value each
+        (probes).  i, j: integer sequences or numpy arrays (mgx_dense_points: a
+        bad index raises and names k), or int64 device tensors, with a float64
+        device tensor out or a new one (mgx_dense_points_device: a bad index
+        gives NaN there)."""
+        if not isinstance(i, (np.ndarray, list, tuple)):
+            import torch
+            if i.dtype != torch.int64 or j.dtype != torch.int64 or i.numel() != j.numel() \
+                    or not i.is_contiguous() or not j.is_contiguous():
+                raise ValueError("i, j: contiguous int64 device tensors of one length")
+            npts = i.numel()
+            out = torch.empty(npts, dtype=torch.float64, device=i.device) if out is None else out
+            check(lib().mgx_dense_points_device(self._h, int(order), float(tau), npts,
+                                                i.data_ptr(), j.data_ptr(),
+                                                _lib.device_ptr(out, npts, "out")))
+            return out
+        pi = np.ascontiguousarray(i, dtype=np.int64)
+        pj = np.ascontiguousarray(j, dtype=np.int64)
+        if pi.shape != pj.shape or pi.ndim != 1:
+            raise ValueError("i, j: one-dimensional index arrays of one length")
+        out = np.empty(pi.size, dtype=np.float64) if out is None else out
+        if out.size != pi.size:
+            raise ValueError(f"out must hold {pi.size} doubles")
+        check(lib().mgx_dense_points(self._h, int(order), float(tau), pi.size,
+                                     pi.ctypes.data, pj.ctypes.data, _np_ptr(out)))
+        return out
+
     def cfl(self):
         """The CFL number max(max|v1|, max|v2|) * dt * N of the finest level's
         velocity, from two stats() passes (multiplied in that order)."""

@@ -346,7 +346,7 @@ int mgx_get_tuning(const char *key, long *value);
  * profiles are stamped with) and of every product source (those + ctx.h,
  * plan.h, sepvel.h, mgx.hip, dist.hip, vfactor.h, vfactor.hip, source.h,
  * source.hip, diag.h, diag.hip, boundary.h, boundary.hip, tstep.h, tstep.hip,
- * bdf.h, bdf.hip, errest.h, errest.hip, include/mgx.h). */
+ * bdf.h, bdf.hip, errest.h, errest.hip, dense.h, dense.hip, include/mgx.h). */
 const char *mgx_build_id(void);
 const char *mgx_build_sources_id(void);
 
@@ -989,6 +989,101 @@ int mgx_step_error_rows(mgx_ctx *ctx, int part, double atol, double rtol, mgx_st
 int mgx_step_err_merge(mgx_step_err *into, const mgx_step_err *other);
 int mgx_array_step_error(const double *u, const double *h, const double *h2, long n, double w,
                          double atol, double rtol, mgx_step_err *out);
+
+/* ---- Dense output: time-interpolated fields, samples and point probes ----------
+ * An adaptive loop produces solutions at the times its controller chooses;
+ * frames, coarse pictures and sensor readings are wanted at times the caller
+ * chooses (the t_eval / dense_output of an ODE library).  After any step the
+ * levels lie in HBM already -- u = u^(n+1), h = u^n and, at depth 2, h2 =
+ * u^(n-1), with dt_prev and dt_prev2 known to the context -- and one pass
+ * (csrc/dense.hip, part of mgx_build_sources_id) evaluates the interpolant
+ * through them at a time inside the last step, without a download and without
+ * clipping dt to land on the output time.
+ *
+ * Meaning, bit for bit.  tau = t* - t^(n+1) <= 0 is the offset of the output
+ * time from the newest level; dt1 = dt_prev and dt2 = dt_prev2 as
+ * mgx_history_info and mgx_history_depth report them.  All C doubles, every
+ * operation rounded, nothing contracted, in either fp_mode.
+ * mgx_dense_weights(order, tau, dt1, dt2, &w0, &w1, &w2), host only:
+ *   order 0:  w0 = 1, w1 = w2 = 0
+ *   order 1:  linear through u and h:  w1 = (0.0 - tau) / dt1, w0 = 1.0 - w1,
+ *             w2 = 0; dt2 is ignored
+ *   order 2:  the Lagrange quadratic on the nodes 0, -dt1, -(dt1+dt2): with
+ *             s = dt1 + dt2, a = tau + dt1, b = tau + s
+ *                 w0 = (a * b) / (dt1 * s)
+ *                 w1 = ((0.0 - tau) * b) / (dt1 * dt2)
+ *                 w2 = (tau * a) / (s * dt2)
+ * MGX_E_ARG for an order outside 0..2, a non-finite tau, dt1 non-finite or not
+ * positive at order >= 1, dt2 non-finite or not positive at order 2.  Any output
+ * pointer may be NULL.  A tau outside [-dt1, 0] (order 2: [-(dt1+dt2), 0])
+ * extrapolates; that is the caller's business and nothing is refused.
+ * At a point
+ *   order 0:  out = u, the same bits
+ *   order 1:  out = fl( fl(w0*u) + fl(w1*h) )
+ *   order 2:  out = fl( fl( fl(w0*u) + fl(w1*h) ) + fl(w2*h2) )
+ * Order 1 does not read h2 and order 0 reads neither history array.  tau = 0
+ * gives the weights (1, 0, 0) exactly at every order, so the output equals u by
+ * value (the sign of a zero is not promised at order >= 1).
+ *
+ * Entry points.  All check their arguments and the context's state before any
+ * device call and report MGX_E_ARG with a message that starts with the
+ * function's own name.
+ * mgx_dense_output(ctx, order, tau, stride, out) / mgx_dense_output_device:
+ * out[a*(m+1)+b] = interpolant(a*stride, b*stride), m = N/stride -- the layout
+ * and rules of mgx_sample / mgx_sample_device at level 0; stride divides N, and
+ * stride 1 is the whole field in the reference layout, ring included.  The
+ * host variant gathers into a compact device buffer and copies once.
+ * mgx_dense_output_rows(ctx, part, order, tau, stride, out, &first_row, &rows):
+ * the owned-rows form with the rules of mgx_sample_rows; any context (a
+ * single-GPU context has part 0); out == NULL only reports first_row and rows.
+ * mgx_dense_points(ctx, order, tau, npts, pi, pj, out): host index arrays and a
+ * host out, out[k] = interpolant(pi[k], pj[k]), 0 <= pi, pj <= N; on an RCCL
+ * rank every point must lie in the rank's owned rows; a bad index is MGX_E_ARG
+ * and the message names k.  mgx_dense_points_device: device index arrays and a
+ * device out; no host validation is possible, so the kernel writes NaN for an
+ * index that is out of range or not held, and reads nothing for that entry.
+ * npts = 0 is a no-op.  The index and value staging of the host form belongs to
+ * the context, grows on demand and is freed by mgx_destroy.
+ * Raw op mgx_array_dense(out, u, h, h2, n, w0, w1, w2, levels): device pointers,
+ * reference layout, any n >= 1, null stream; synchronises.  levels (1 to 3) says
+ * how many inputs are read -- the point formula of order levels - 1 with the
+ * given weights; levels 1 copies u and reads no weight -- and the unused
+ * pointers may be NULL.
+ *
+ * State.  Order >= 1 needs a history that is on and valid; order 2 needs depth
+ * 2 with both valid and valid2.  Nothing else is checked: after a depth-2
+ * rollback that kept valid, order 1 interpolates between u^(n-1) and u^n, which
+ * is right.  u is read by the route mgx_field_stats takes (the level is
+ * materialised, a packed pre-smoothed u expanded); pending and speculative
+ * state is left alone, as the downloads leave it.  The weights use dt_prev and
+ * dt_prev2, not the context's current dt: a mgx_set_time_step between the step
+ * and the output call changes nothing.
+ * Contexts, as mgx_sample*: single-GPU and local-parts contexts take the
+ * whole-grid calls (each part writes its owned rows, sub-context 0 when every
+ * level is replicated); an RCCL rank gets MGX_E_ARG from
+ * mgx_dense_output[_device] and uses the rows form.  No call communicates.
+ * Accounting: compulsory bytes 8 * (levels + 1) per output point (gathered
+ * point at stride > 1), levels = order + 1; the read-only tuning keys
+ * "dense_us" / "dense_bytes" (mgx_get_tuning) give the device microseconds and
+ * bytes of the calling thread's last dense call, as "errest_us" /
+ * "errest_bytes" do.  There is no profile kind for it.  Tuning keys of the
+ * stride-1 pass (the same bits for every value): "dense_store" 0 (default) =
+ * plain stores, 1 = non-temporal stores, 2 = one 16-byte store per column pair
+ * on every row; "dense_rows" = the rows of a workgroup (default 4; 0 = the row
+ * groups of the error pass).  Measured at N=16384 on one MI355X:
+ * DESIGN.md section 15. */
+int mgx_dense_weights(int order, double tau, double dt1, double dt2, double *w0, double *w1,
+                      double *w2);
+int mgx_dense_output(mgx_ctx *ctx, int order, double tau, long stride, double *out);
+int mgx_dense_output_device(mgx_ctx *ctx, int order, double tau, long stride, double *out);
+int mgx_dense_output_rows(mgx_ctx *ctx, int part, int order, double tau, long stride, double *out,
+                          long *first_row, long *rows);
+int mgx_dense_points(mgx_ctx *ctx, int order, double tau, long npts, const long *pi,
+                     const long *pj, double *out);
+int mgx_dense_points_device(mgx_ctx *ctx, int order, double tau, long npts, const long *pi,
+                            const long *pj, double *out);
+int mgx_array_dense(double *out, const double *u, const double *h, const double *h2, long n,
+                    double w0, double w1, double w2, int levels);
 
 #ifdef __cplusplus
 }
