@@ -203,6 +203,8 @@ _SIGS = {
     "mgx_dense_points": (_I, [_vp, _I, _D, _L, _vp, _vp, _vp]),
     "mgx_dense_points_device": (_I, [_vp, _I, _D, _L, _vp, _vp, _vp]),
     "mgx_array_dense": (_I, [_vp, _vp, _vp, _vp, _L, _D, _D, _D, _I]),
+    "mgx_set_predictor": (_I, [_vp, _I]),
+    "mgx_predictor_info": (_I, [_vp, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), _dp]),
     "mgx_build_id": (C.c_char_p, []),
     "mgx_build_sources_id": (C.c_char_p, []),
 }

@@ -124,6 +124,13 @@ struct mgx_ctx {
     bool hist2_on = false, hist2_valid = false, hist_rolled = false;
     double hist2_dt = 0;
     void hist_invalidate() { hist_valid = hist2_valid = hist_rolled = false; }
+    // mgx_set_predictor (csrc/predict.h): pred_order = the setting (0 off); the
+    // record of the last mgx_step_bdf2 -- pred_last its effective order (0: it
+    // ran unpredicted), pred_adopted: it started from the guess, pred_res the
+    // guess's residual norm
+    int pred_order = 0, pred_last = 0;
+    bool pred_adopted = false;
+    double pred_res = 0;
     mgx_options opt{};
     std::vector<mgxi::Level> lv;
     double *partials = nullptr;   // norm partial sums
@@ -303,6 +310,12 @@ int hist_alloc_ctx(mgx_ctx *c, const char *who);
 void hist_free_ctx(mgx_ctx *c);
 int hist_snapshot_ctx(mgx_ctx *c);
 int op_rhs_norm_bdf(mgx_ctx *c, double b0, double b1, double cf, double *res0);
+// the same pass with a predicted start (csrc/predict.h; single-GPU contexts):
+// rhs, the guess of effective order e (weights w) into level 0's free buffer,
+// *res0 = |rhs - A u|, *resp = |rhs - A g|.  Stores no snapshot: the caller
+// moves the history on by exchanging pointers (mgx_step_bdf2).
+int op_predict_bdf(mgx_ctx *c, double b0, double b1, double cf, int e, const double w[3],
+                   double *res0, double *resp);
 int hist_restore_ctx(mgx_ctx *c);
 // ... and on a partitioned context (dist.hip): every part's owned rows, or
 // every sub-context where all levels are replicated.  dist_rhs_norm_bdf mirrors

@@ -25,6 +25,7 @@
 #include "bdf.h"
 #include "errest.h"
 #include "dense.h"
+#include "predict.h"
 #include "vfactor.h"
 
 namespace mgxi {
@@ -987,6 +988,38 @@ int op_rhs_norm_bdf(mgx_ctx *c, double b0, double b1, double cf, double *res0) {
     return read_norm(c, res0);
 }
 
+// The same pass with a predicted start (csrc/predict.hip): the guess goes to the
+// free buffer of level 0 (free wherever op_rhs_norm_pre's is), nothing is stored
+// into the history, and two norms come back in one read.
+int op_predict_bdf(mgx_ctx *c, double b0, double b1, double cf, int e, const double w[3],
+                   double *res0, double *resp) {
+    drop_spec(c);
+    CHK(materialize(c, 0));
+    CHK(op_expand(c));   // (as mgx_download: h becomes what it would return)
+    Level &L = c->lv[0];
+    double cb = 0;
+    mgxsrc::SrcArgs A = source_args(c, true, &cb);   // (f and terms unset: no source)
+    A.c = L.coef;
+    A.cf = cf;
+    const bool field = A.f && !A.terms;
+    // u, h (, h2) in, g and rhs out (+ f of a field source) (+ v1, v2 without factors)
+    cb = (8.0 * (3 + e) + (A.sa1 ? 0.0 : 16.0) + (field ? 8.0 : 0.0)) * L.M();
+    // the BDF pass, the second residual, the guess (e + 1 reads, one write)
+    const double bytes = ((field ? 96.0 : 88.0) + 48.0 + 8.0 * (e + 2)) * L.M();
+    double *gout = L.u[L.nxt()];
+    CHK(launch(c, MGX_K_RHS, 0, bytes, cb, [&] {
+        mgxpred::launch_predict_bdf(A, c->hist, e == 2 ? c->hist2 : nullptr, e, w, gout, b0, b1,
+                                    c->stream);
+    }));
+    L.packed[L.nxt()] = false;
+    HIPCHK(hipMemcpyAsync(c->hscal, c->dscal, 2 * sizeof(double), hipMemcpyDeviceToHost,
+                          c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    *res0 = c->hscal[0];
+    *resp = c->hscal[1];
+    return MGX_OK;
+}
+
 // mgx_set_history on one context's own state
 int hist_alloc_ctx(mgx_ctx *c, const char *who) {
     if (c->hist) return MGX_OK;
@@ -1168,19 +1201,22 @@ long g_post_only = 10;
 // store, always recompute: the test of the recompute path)
 double g_post_predict = 10.0;
 
+// start_res: the norm of the u the loop starts from where that is not the u of
+// res0 (a predicted start, mgx_set_predictor): the criterion keeps res0, the
+// loop and the extrapolation of "post_predict" / "post_only" begin at start_res
 int op_mg_outer(mgx_ctx *c, double tol, int *cycles, double *res0_out, double *res_out,
-                const double *have_res0 = nullptr) {
+                const double *have_res0 = nullptr, const double *start_res = nullptr) {
     double res0 = 0, res = 0;
     if (have_res0)
         res0 = *have_res0;
     else
         CHK(norm0(c, &res0));
-    res = res0;
+    res = start_res ? *start_res : res0;
     int iter = 0;
     // the u_post of a cycle that does not converge is never observed: the
     // cross pass skips storing it (2.15 GB at N=16384) when so predicted
     const bool predict = g_post_predict != 0 && post_predictable(c);
-    double prev = res0;
+    double prev = res;
     for (; iter < c->opt.max_cycle && res / res0 > tol; ++iter) {
         bool store = true, last = false;
         if (predict) {
@@ -2957,6 +2993,75 @@ int mgx_history_info(mgx_ctx *c, int *on, int *valid, double *dt_prev, double *k
     if (k_solve) *k_solve = c->k_solve();
     return MGX_OK;
 }
+// A BDF2 step with a predicted start (mgx_set_predictor; csrc/predict.h) on a
+// single-GPU context with no ring pending.  The pass reads u^n, u^(n-1) (and
+// u^(n-2)) at stencil neighbours and writes the guess into level 0's free
+// buffer, so no array it reads may be written by it: the history moves on by an
+// exchange of pointers.  Every array in the exchange is a finest-level array of
+// pitch * (n + 1) doubles from its own hipMalloc (create_ctx, hist_alloc_ctx,
+// hist2_alloc_ctx) whose padding columns are zeros -- each has been zeroed or a
+// whole copy of u -- and nothing holds a level-0 u pointer across calls (the
+// captured sub-cycles start at level >= 1; every pass takes L.U(), hist and
+// hist2 at call time).
+static int step_bdf2_predicted(mgx_ctx *c, const mgxbdf::Coefs &K, double cf, double tol,
+                               int *cycles, double *res0_out, double *res_out) {
+    const int e = c->pred_order == 2 && c->hist2_on && c->hist2_valid ? 2 : 1;
+    double w[3];
+    if (mgxdense::weights(e, c->dt, c->hist_dt, c->hist2_dt, w) != 0)
+        return fail(MGX_E_INTERNAL, "mgx_step_bdf2: the predictor's weights");
+    double r0 = 0, rp = 0;
+    CHK(op_predict_bdf(c, K.b0, K.b1, cf, e, w, &r0, &rp));
+    Level &L = c->lv[0];
+    if (!L.u[L.cur] || !L.u[L.nxt()] || !c->hist || (c->hist2_on && !c->hist2))
+        return fail(MGX_E_INTERNAL, "mgx_step_bdf2: a finest-level array is missing");
+    // the buffer of u^n becomes hist, the old hist becomes hist2 (depth 2), and
+    // the oldest history array takes u^n's place among level 0's buffers
+    double *un = L.u[L.cur], *spare = nullptr;
+    if (c->hist2_on) {
+        spare = c->hist2;
+        c->hist2 = c->hist;
+        c->hist2_valid = true;
+        c->hist2_dt = c->hist_dt;
+    } else {
+        spare = c->hist;
+    }
+    c->hist = un;
+    L.u[L.cur] = spare;
+    L.packed[L.cur] = false;
+    c->hist_rolled = false;
+    c->hist_dt = c->dt;
+    const bool adopted = rp < r0;   // (false where rp is NaN)
+    c->pred_last = e;
+    c->pred_adopted = adopted;
+    c->pred_res = rp;
+    if (adopted) {
+        L.cur = L.nxt();   // the guess
+    } else {
+        // refused: u^n is both u and h -- one copy, as a theta-step's snapshot
+        const size_t bytes = sizeof(double) * (size_t)(L.n + 1) * (size_t)L.pitch;
+        HIPCHK(hipMemcpyAsync(L.u[L.cur], c->hist, bytes, hipMemcpyDeviceToDevice, c->stream));
+    }
+    L.zero = false;
+    return op_mg_outer(c, tol, cycles, res0_out, res_out, &r0, adopted ? &rp : nullptr);
+}
+int mgx_set_predictor(mgx_ctx *c, int order) {
+    if (!c) return fail(MGX_E_ARG, "mgx_set_predictor: null ctx");
+    if (order < 0 || order > 2)
+        return fail(MGX_E_ARG, "mgx_set_predictor: order must be 0, 1 or 2");
+    if (order > 0 && c->dist)
+        return fail(MGX_E_ARG, "mgx_set_predictor: a partitioned context takes order 0 only (the "
+                               "guess would need a ghost-row exchange)");
+    c->pred_order = order;
+    return MGX_OK;
+}
+int mgx_predictor_info(mgx_ctx *c, int *order, int *last_order, int *adopted, double *res_pred) {
+    if (!c) return fail(MGX_E_ARG, "mgx_predictor_info: null ctx");
+    if (order) *order = c->pred_order;
+    if (last_order) *last_order = c->pred_last;
+    if (adopted) *adopted = c->pred_adopted ? 1 : 0;
+    if (res_pred) *res_pred = c->pred_last ? c->pred_res : 0.0;
+    return MGX_OK;
+}
 int mgx_step_bdf2(mgx_ctx *c, double tol, int *cycles, double *res0_out, double *res_out) {
     if (!c) return fail(MGX_E_ARG, "mgx_step_bdf2: null ctx");
     if (!c->hist_on)
@@ -2969,6 +3074,12 @@ int mgx_step_bdf2(mgx_ctx *c, double tol, int *cycles, double *res0_out, double 
     if (K.kA != c->k_solve()) CHK(set_solve_k(c, K.kA));
     HIPCHK(hipSetDevice(c->device));
     drop_step_spec(c);
+    c->pred_last = 0;
+    c->pred_adopted = false;
+    c->pred_res = 0;
+    // (a step that takes a pending ring runs unpredicted, launch for launch)
+    if (c->pred_order > 0 && !c->bc_pending && !c->dist)
+        return step_bdf2_predicted(c, K, cf, tol, cycles, res0_out, res_out);
     // rhs, h <- u^n and mg_outer's initial norm in one pass
     double res0 = 0;
     if (c->hist2_on) {

@@ -372,6 +372,28 @@ class Multigrid:
         theta-step: call step() next."""
         check(lib().mgx_rollback(self._h))
 
+    # -- a predicted start for BDF2 steps (mgx_set_predictor)
+    def set_predictor(self, order):
+        """mgx_set_predictor: 0 = off (the default), 1 / 2 = step_bdf2 forms a
+        linear / quadratic guess of u^(n+1) from the resident history and
+        starts from it where its residual is smaller than u^n's; the stopping
+        criterion stays relative to u^n's residual.  Order 2 needs depth 2 and
+        two steps of history and falls back to order 1 by itself.  A step that
+        takes a pending ring runs unpredicted.  Single-GPU contexts only: a
+        partitioned context raises MGXError (MGX_E_ARG) for an order > 0."""
+        check(lib().mgx_set_predictor(self._h, int(order)))
+
+    def predictor_info(self):
+        """-> dict(order, last_order, adopted, res_pred) (mgx_predictor_info):
+        the setting; the effective order of the last step_bdf2 (0: it ran
+        unpredicted); whether that step started from the guess; the guess's
+        residual norm (0.0 where last_order is 0)."""
+        o, lo, ad, rp = C.c_int(), C.c_int(), C.c_int(), C.c_double()
+        check(lib().mgx_predictor_info(self._h, C.byref(o), C.byref(lo), C.byref(ad),
+                                       C.byref(rp)))
+        return {"order": o.value, "last_order": lo.value, "adopted": ad.value,
+                "res_pred": rp.value}
+
     # -- the step error estimate on a two-deep history (mgx_set_history_depth)
     def set_history_depth(self, depth):
         """mgx_set_history_depth: 0 = no history, 1 = set_history(), 2 = a

@@ -346,7 +346,8 @@ int mgx_get_tuning(const char *key, long *value);
  * profiles are stamped with) and of every product source (those + ctx.h,
  * plan.h, sepvel.h, mgx.hip, dist.hip, vfactor.h, vfactor.hip, source.h,
  * source.hip, diag.h, diag.hip, boundary.h, boundary.hip, tstep.h, tstep.hip,
- * bdf.h, bdf.hip, errest.h, errest.hip, dense.h, dense.hip, include/mgx.h). */
+ * bdf.h, bdf.hip, errest.h, errest.hip, dense.h, dense.hip, predict.h,
+ * predict.hip, include/mgx.h). */
 const char *mgx_build_id(void);
 const char *mgx_build_sources_id(void);
 
@@ -1084,6 +1085,64 @@ int mgx_dense_points_device(mgx_ctx *ctx, int order, double tau, long npts, cons
                             const long *pj, double *out);
 int mgx_array_dense(double *out, const double *u, const double *h, const double *h2, long n,
                     double w0, double w1, double w2, int levels);
+
+/* ---- A predicted start for BDF2 steps from the resident history ----------------
+ * After a step u^n, u^(n-1) and, at depth 2, u^(n-2) lie on the device, yet a
+ * solve starts from u^n.  mgx_set_predictor(ctx, order) makes mgx_step_bdf2
+ * form a guess g of u^(n+1) from them and start from whichever of u^n and g has
+ * the smaller residual.  order 0 = off (the default), 1 = linear, 2 =
+ * quadratic.  MGX_E_ARG before any device call, with a message that starts with
+ * the function's name: a NULL ctx, an order outside 0..2, order > 0 on a
+ * partitioned context (local parts and RCCL ranks alike: the guess would need a
+ * ghost-row exchange).  Order 0 is accepted everywhere.  The call allocates
+ * nothing, drops nothing and needs no history yet.  The setting belongs to the
+ * context: it survives mgx_upload*, mgx_set_velocity*, mgx_set_source*,
+ * mgx_set_time_step and mgx_rollback.  A context that never calls it launches
+ * exactly what it launched before the predictor existed.
+ * Only mgx_step_bdf2 changes, only while order > 0, and only on a step with no
+ * ring pending from MGX_BC_NEXT_STEP: a step that takes a pending ring runs bit
+ * for bit and launch for launch as with the predictor off.  mgx_step[_ex],
+ * mgx_timestepper* and the raw ops are untouched.
+ * The effective order e of a step is 2 when order 2 is set, the history is at
+ * depth 2 and valid2 holds (mgx_history_depth), otherwise 1 -- a run that has
+ * just started or has just been rolled back predicts linearly by itself.
+ * The guess is the dense-output interpolant one step ahead: with (w0, w1, w2) =
+ * mgx_dense_weights(e, tau = +dt, dt_prev, dt_prev2), dt the context's step and
+ * dt_prev / dt_prev2 as they stand before the step, on rows and columns
+ * 1..N-1
+ *     e = 1:  g = fl( fl(w0 u) + fl(w1 h) )
+ *     e = 2:  g = fl( fl( fl(w0 u) + fl(w1 h) ) + fl(w2 h2) )
+ * (u = u^n, h = u^(n-1), h2 = u^(n-2); every operation rounded, none
+ * contracted, in either fp_mode) and on the ring g = u, the same bits: what
+ * mgx_array_dense computes.  At e = 1 it is also, bit for bit, the `up` that
+ * mgx_step_error forms after the step, so the d of its record is then corrector
+ * minus predictor.
+ * The step: coefficients and right-hand side as without the predictor (rhs has
+ * the same bits); r0 = |rhs - A u^n| and rp = |rhs - A g|, both in the
+ * reference's term order with k = kA -- r0 is bit for bit the res0 the same
+ * step returns with the predictor off; the history moves on as without it (h =
+ * what mgx_download returned before the step, ring included; at depth 2 h2 =
+ * the old h; valid flags and dt_prev values alike).  adopted = (rp < r0), false
+ * when rp is NaN: u becomes g and the cycles start with res = rp; otherwise u
+ * stays u^n and res = r0.  The loop is mg_outer's, while (iter < max_cycle &&
+ * res / r0 > tol): the reference norm stays r0, the plain start's, so a
+ * predicted step ends on the criterion a plain step ends on and zero cycles is
+ * a legal outcome.  *res0 = r0; *res = the last norm, rp when no cycle ran.
+ * MGX_E_NOCONV as without the predictor.
+ * mgx_predictor_info: any pointer may be NULL.  order = the setting;
+ * last_order = the effective order of the context's last mgx_step_bdf2, 0 if
+ * none has run, the predictor was off or the step took a pending ring; adopted
+ * = that step started from the guess; res_pred = rp, 0 when last_order is 0.
+ * The pass (csrc/predict.hip, part of mgx_build_sources_id; profile kind
+ * MGX_K_RHS) is one row march that forms rhs, g and both norms; it stores g
+ * into a free finest-level buffer and no snapshot -- the history moves on by an
+ * exchange of buffer pointers, one device copy more on a refused step.
+ * Compulsory bytes per finest point: 8 * (3 + e) with velocity factors, + 16
+ * without, + 8 with a field source; algorithmic bytes: those of the BDF2 pass +
+ * 48 (the second residual) + 8 * (e + 2) (the guess).  Measured: DESIGN.md
+ * section 16. */
+int mgx_set_predictor(mgx_ctx *ctx, int order);
+int mgx_predictor_info(mgx_ctx *ctx, int *order, int *last_order, int *adopted, double *res_pred);
 
 #ifdef __cplusplus
 }
